@@ -11,12 +11,24 @@ before the timed region.  Multi-GPU = independent batches per rank (weak
 scaling, no collective in the data path); timing is max over ranks.
 
     python bench.py [--gpus N --steps K --warmup W --batch B --workload cfg2|cfg3|cfg4]
+                    [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line on rank 0.  The roofline entry is for the dominant
-kernel (msm_accum), timed with HIP events on its launch stream inside the
-timed region.  cpu_baseline times the C oracle (oracle/liboracle.so, a
+Prints ONE JSON line on rank 0.  A plain run does only what the headline
+needs: setup (SRS, fixed-base table, inputs), W warmup steps, K timed steps,
+the line.  The roofline entry is for the dominant kernel (msm_accum), timed
+with HIP events on its launch stream inside the timed region.
+
+--full adds everything else, with the fields a plain run leaves null: the
+parity check of every output of the last step, the default-table, Pippenger,
+latency, setup and table-curve legs, the clock probe, the VALU
+microbenchmarks, the kernel identity and counter traffic of the roofline
+entry, and cpu_baseline, which times the C oracle (oracle/liboracle.so, a
 restatement of the reference's naive per-term polyeval_G1) on a bounded
 sample on one host core.
+
+--dump-outputs DIR writes the outputs of the last timed step (seeded inputs,
+so identical from run to run) as DIR/<name>.npy: float64 arrays holding the
+32-bit words of the points, flags and evaluations.
 """
 from __future__ import annotations
 
@@ -105,7 +117,34 @@ def parse():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="--scaling strong: polynomials (openings for cfg3) per step over all ranks "
                          "(default 8 x the per-GPU default batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the parity check of the last step, the "
+                         "default-table / Pippenger / latency / setup / table-curve legs (each still has its "
+                         "--no-* switch), the CPU baseline, the clock probe, the VALU microbenchmarks and the "
+                         "kernel identity + counter traffic of the roofline entry.  Without it the run sets up, "
+                         "warms up, times --steps steps and prints the line with those fields null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (commit and proof points, "
+                         "infinity flags, evaluations) as DIR/<name>.npy, float64 arrays of the results' 32-bit "
+                         "words (exact); inputs are seeded, so two builds can be compared output for output")
     return ap.parse_args()
+
+
+def words_f64(a):
+    """an integer array as float64 of its little-endian 32-bit words (every
+    word is exact in a double): (..., k) 64-bit limbs -> (..., 2k)"""
+    a = np.ascontiguousarray(a)
+    if a.dtype.itemsize == 8:
+        return a.view(np.uint32).astype(np.float64)
+    return a.astype(np.float64)
+
+
+def dump_outputs(path, arrays, rank=0):
+    """--dump-outputs: one .npy per output of the last timed step (rank 0
+    writes <name>.npy, any other rank <name>_rank<r>.npy)"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ("" if rank == 0 else "_rank%d" % rank) + ".npy"), words_f64(a))
 
 
 def curve_consts(curve):
@@ -634,20 +673,22 @@ def main():
     # ("default": the budget-chosen default table of the first 4097 SRS
     # points, built with the SRS) and with that table off ("pippenger": the
     # table-less path, which allocates nothing beyond the SRS like the
-    # reference, src/trusted_setup.cpp:137-142)
+    # reference, src/trusted_setup.cpp:137-142).  --full only, like every
+    # leg, check and probe below that is not the headline's own timed run.
+    full = args.full
     dt = ctx.default_table_info()
     dflt = pip = lat = None
     sec_steps = max(3, min(args.steps, 6))
-    if fixed_bits and not args.no_pippenger and dt[0]:
+    if full and fixed_bits and not args.no_pippenger and dt[0]:
         de, dk, _ = timed_run(ctx, step, streams, sec_steps, 1, world, dist, torch, dev)
         dflt = {"value": units_all * sec_steps / de, "ms_per_step": de / sec_steps * 1e3,
                 "msm": "default table, c=%d over %d points (%.2f GB)" % (dt[0], dt[1], dt[2] / 1e9),
                 "kernel_ms_per_step": {k: v[0] / sec_steps for k, v in dk.items()}}
-    if not args.no_latency and args.workload != "cfg3":
+    if full and not args.no_latency and args.workload != "cfg3":
         lat = {"default": latency_leg(ctx, coeffs_h),
                "default_table": {"window_bits": dt[0], "points": dt[1], "bytes": dt[2]}}
     ctx.set_default_table(0)  # off from here on: the main table serves the rest
-    if fixed_bits and not args.no_pippenger:
+    if full and fixed_bits and not args.no_pippenger:
         pe, pk, _ = timed_run(ctx, step, streams, sec_steps, 1, world, dist, torch, dev)
         pip = {"value": units_all * sec_steps / pe, "ms_per_step": pe / sec_steps * 1e3,
                "msm": "pippenger, c=%d, segment %d" % (args.window_bits, args.segment),
@@ -656,7 +697,7 @@ def main():
         lat["pippenger"] = latency_leg(ctx, coeffs_h)
 
     setup = None
-    if rank == 0 and world == 1 and not args.no_setup and args.workload != "cfg3":
+    if full and rank == 0 and world == 1 and not args.no_setup and args.workload != "cfg3":
         try:
             setup = setup_leg(kzgx, curve, K, C, tau)
         except Exception as e:  # noqa: BLE001 -- a secondary leg, never fatal for the headline
@@ -677,18 +718,23 @@ def main():
         ctx.set_fixed_points_per_thread(args.fixed_ppt)
 
     elapsed, kern, local_s = timed_run(ctx, step, streams, args.steps, args.warmup, world, dist, torch, dev)
+    if args.dump_outputs:
+        outs = {"proof_xy": bufs.d_pout, "proof_inf": bufs.d_pinf, "proof_y": bufs.d_y}
+        if args.workload != "cfg3":
+            outs.update({"commit_xy": bufs.d_cout, "commit_inf": bufs.d_cinf})
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in outs.items()}, rank)
 
     # ---- core clock during the step (outside the timed region): a one-wave
     # probe spins on its own stream beside a few more steps (DVFS lowers the
     # clock under this load: profiles/r03_pmc_clock_table_sweep.json) ----
-    step_clock = clock_during(ctx, step, elapsed / args.steps, torch, dev)
+    step_clock = clock_during(ctx, step, elapsed / args.steps, torch, dev) if full else None
     ranks = rank_records(world, rank, local, dev, local_s, dist, torch, {"batch": B})
     dinfo = dist_info(world, dist, torch)
 
     # ---- parity: every output of the last step (oracle identity, MSM-independent) ----
     checked = ok = 0
     bad = None
-    if rank == 0:
+    if full and rank == 0:
         checked, ok, bad = check_step(curve, C, tau, args.workload, coeffs_h, zs_h, bufs, w64)
 
     # ---- throughput vs table size: what a re-linked create_commit gets at
@@ -701,7 +747,7 @@ def main():
     # The curve's own setup_s values after the headline table's release
     # include that wait. ----
     curve_pts = None
-    if fixed_bits and not args.no_table_curve:
+    if full and fixed_bits and not args.no_table_curve:
         curve_pts = [{"window_bits": 0, "gb": 0.0, "value": pip["value"] if pip else None}]
         if fb[0]:
             curve_pts.append({"window_bits": fb[0], "gb": fb[2] / 1e9, "setup_s": t_setup,
@@ -724,7 +770,7 @@ def main():
 
     # ---- CPU baseline (rank 0, N = 1 only) ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0:
         import corc
         corc.build()
         srs = corc.gen_srs(curve, tau, n)
@@ -799,7 +845,7 @@ def main():
             wins = (257 + args.window_bits - 1) // args.window_bits
         # HBM traffic per launch from a counter pass of THIS kernel build
         # (code-object hash), batch and window; null otherwise
-        kid = accum_kernel_id(curve, fb[0]) if fb[0] else {"sha256": None}
+        kid = accum_kernel_id(curve, fb[0]) if full and fb[0] else {"sha256": None}
         tj, tsrc = matching_traffic(args.workload, B, fb[0], kid.get("sha256"))
         traffic = tj.get("msm_accum_bytes_per_launch") if tj else None
         entry_bytes = fb[2] // max(1, wins * fb[1] << (fb[0] - 1)) if fb[0] else 0
@@ -812,8 +858,9 @@ def main():
         mad_peak = None
         mad_ghz = None
         try:
-            peak = ctx.microbench_mixed_add()
-            mad_peak, mad_ghz = ctx.microbench_mad_u64_clock()
+            if full:
+                peak = ctx.microbench_mixed_add()
+                mad_peak, mad_ghz = ctx.microbench_mad_u64_clock()
         except Exception as e:  # noqa: BLE001 -- reported, never fatal for the headline
             print("bench: VALU microbenchmarks unavailable: %s" % e, file=sys.stderr)
         L = 9 if curve == "BN254" else 14
@@ -918,9 +965,11 @@ def main():
                 "ranks": ranks,
                 "dist": dinfo,
             },
-            "parity": {"checked": checked, "ok": int(ok), "first_failure": bad,
-                       "method": "every output of the last step: commit = [P(tau)]G1, proof = [q(tau)]G1, "
-                                 "y = P(z) (C oracle)"},
+            "full": full,
+            "parity": None if not full else {
+                "checked": checked, "ok": int(ok), "first_failure": bad,
+                "method": "every output of the last step: commit = [P(tau)]G1, proof = [q(tau)]G1, "
+                          "y = P(z) (C oracle)"},
             "cpu_baseline": cpu,
             "reference_published": {"commit_ms": REF_COMMIT_S * 1e3, "proof_ms": REF_PROOF_S * 1e3,
                                     "multi_proof_ms": {"128": 922.247, "256": 860.305, "512": 810.811,
@@ -1075,14 +1124,20 @@ def run_cfg5(args, world, rank, local, dev, torch, dist, kzgx):
                       "%s all-gather of the projective partial records (until the stream may use them); fold = "
                       "kzgx_g1_sum_partials_device of the gathered records (the step's one inversion)"
                       % dinfo.get("backend", "no")}
+    full = args.full
+    if args.dump_outputs:
+        # the packed affine record of the commit: x || y || infinity word
+        dump_outputs(args.dump_outputs, {"commit_record": res.cpu().numpy()}, rank)
     if rank == 0:
-        xys, infs = kzgx_dist.unpack_points(res.cpu().numpy(), w64)
-        xy, inf = xys[0], bool(infs[0])
-        got = None if inf else (to_int(xy[:4]), to_int(xy[4:8]))
-        ptau = 0
-        for c in reversed([to_int(r) for r in coeffs_h]):
-            ptau = (ptau * tau + c) % C.r
-        ok = got == K.scalar_mul(C, (C.gx, C.gy), ptau)
+        ok = None
+        if full:
+            xys, infs = kzgx_dist.unpack_points(res.cpu().numpy(), w64)
+            xy, inf = xys[0], bool(infs[0])
+            got = None if inf else (to_int(xy[:4]), to_int(xy[4:8]))
+            ptau = 0
+            for c in reversed([to_int(r) for r in coeffs_h]):
+                ptau = (ptau * tau + c) % C.r
+            ok = got == K.scalar_mul(C, (C.gx, C.gy), ptau)
         ms_per_step = elapsed / args.steps * 1e3
         # algorithmic bytes of one commit: n (affine point + 32 B scalar) + affine out
         P_b = 2 * w64 * 8
@@ -1096,11 +1151,12 @@ def run_cfg5(args, world, rank, local, dev, torch, dist, kzgx):
         madd_rate = n * wins / (ms_per_step * 1e-3)  # all ranks' mixed additions per second
         peak = None
         try:
-            peak = ctx.microbench_mixed_add() * world  # measured on this rank's GPU, times the ranks
+            if full:
+                peak = ctx.microbench_mixed_add() * world  # measured on this rank's GPU, times the ranks
         except Exception as e:  # noqa: BLE001 -- reported, never fatal for the headline
             print("bench: mixed-add microbenchmark unavailable: %s" % e, file=sys.stderr)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0:
+        if full and world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0:
             # the naive CPU commit of 2^20 + 1 terms takes minutes, so
             # time the first 2^14 terms and scale linearly (the algorithm is one
             # independent scalar multiplication per term)
@@ -1168,7 +1224,8 @@ def run_cfg5(args, world, rank, local, dev, torch, dist, kzgx):
                 "ranks": ranks,
                 "dist": dinfo,
             },
-            "parity": {"checked": 1, "ok": int(ok), "method": "[P(tau)]G1 identity"},
+            "full": full,
+            "parity": None if not full else {"checked": 1, "ok": int(ok), "method": "[P(tau)]G1 identity"},
             "cpu_baseline": cpu,
         }
         print(json.dumps(line), flush=True)
@@ -1225,7 +1282,11 @@ def run_common(args, world, rank, local, dev, torch, dist, kzgx):
                      "commit_ok": got == exp, "verified": verified})
         print("common: degree %8d commit %8.3f ms proof %8.3f ms verify %7.3f ms %s" % (
             degree, commit_ms, proof_ms, verify_ms, "ok" if ok else "MISMATCH"), file=sys.stderr, flush=True)
+        last = {"commit_xy": cxy, "commit_inf": np.array([cinf], dtype=np.int32), "proof_xy": pxy,
+                "proof_inf": np.asarray(pinf, dtype=np.int32), "proof_y": y}
         degree *= 2
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)  # the largest degree's commit and opening
     top = rows[-1]
     line = {
         "metric": "KZG single commit/proof/verify latency, BN254, 10,429,000-point setup (benchmark-common)",

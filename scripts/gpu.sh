@@ -9,7 +9,8 @@
 #   micro[:BIN]       scripts/mb/BIN (mixed-add variants; default: all)
 #   tests[:K]         pytest -m gpu (optionally -k K, commas -> spaces)
 #   smoke             __graft_entry__.smoke()
-#   bench[:ARGS]      python bench.py ARGS (commas -> spaces)
+#   bench[:ARGS]      python bench.py ARGS (commas -> spaces; --full among them for the parity check,
+#                     the secondary legs and the roofline's kernel identity, which the pmc passes need)
 #   prof[:ARGS]       rocprofv3 --kernel-trace --stats around bench.py ARGS
 #   pmc:CTRS[:ARGS]   one rocprofv3 --pmc pass (CTRS comma-separated) around bench.py ARGS
 #   py:SCRIPT[,ARGS]  python3 scripts/SCRIPT ARGS

@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B of two builds of libkzgx.so on one box, interleaved:
 #   bash scripts/gpu_ab.sh TAG LIB_A LIB_B "bench args (commas)" [rounds]
+# bench.py runs with --full (the parity of every output is printed per run).
 # LIB_A / LIB_B: a libkzgx.so path, optionally followed by environment
 # settings for that side: path+VAR=value+VAR2=value
 set -o pipefail
@@ -14,7 +15,7 @@ for r in $(seq 1 "$R"); do
     IFS=+ read -r lib envs <<< "$spec"
     envargs=()
     [[ -n "$envs" ]] && IFS=+ read -r -a envargs <<< "$envs"
-    env KZGX_LIB="$lib" "${envargs[@]}" timeout -k 10 500 python -u bench.py $ARGS > "$OUT/${v}_$r.json" \
+    env KZGX_LIB="$lib" "${envargs[@]}" timeout -k 10 500 python -u bench.py --full $ARGS > "$OUT/${v}_$r.json" \
       2> "$OUT/${v}_$r.err" || { tail -20 "$OUT/${v}_$r.err"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open('$OUT/${v}_$r.json').read().strip().splitlines()[-1]); print('$v', $r, round(d['value']), d['parity'])"
   done

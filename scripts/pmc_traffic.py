@@ -5,7 +5,7 @@
 
 reads gpurun_out/TAG/pmc_<RD_STEP>/ (TCC_EA0_RDREQ_{32B,64B,128B}_sum) and
 gpurun_out/TAG/pmc_<WR_STEP>/ (WRITE_SIZE), the passes `scripts/gpu.sh`'s
-`pmc` step runs around `bench.py --serial`, and writes
+`pmc` step runs around `bench.py --full --serial`, and writes
 profiles/<ROUND>_pmc_traffic_<WORKLOAD>.json.
 
 The request-size counters give DRAM bytes directly (every read of this kernel
@@ -84,7 +84,7 @@ def main():
         "kernel_code_bytes": kid.get("bytes"),
         "git_head": head,
         "source": "rocprofv3 --pmc TCC_EA0_RDREQ_{32B,64B,128B}_sum (pass %s), then --pmc WRITE_SIZE (pass %s), "
-                  "each on bench.py --serial (gpurun_out/%s, scripts/gpu.sh pmc steps); mean over %d dispatches"
+                  "each on bench.py --full --serial (scripts/gpu.sh pmc steps, tag %s); mean over %d dispatches"
                   % (rd, wr, tag, rdc.get("TCC_EA0_RDREQ_128B_sum", (0, 0))[1]),
         "rdreq_128B_per_launch": n128,
         "rdreq_64B_per_launch": n64,

@@ -29,7 +29,7 @@ fetch_raw = acc["FETCH_SIZE"]["mean_per_dispatch"] * 1024
 write = acc["WRITE_SIZE"]["mean_per_dispatch"] * 1024
 tr = {
     "workload": "cfg2", "batch": batch, "kernel": "k_fixed_accum<BN254G1,16>",
-    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on bench.py --serial --steps 2 "
+    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on bench.py --full --serial --steps 2 "
               "--warmup 1; scripts/summarize_pmc.py",
     "fetch_size_raw_bytes": fetch_raw,
     "fetch_bytes_corrected": 2 * fetch_raw,

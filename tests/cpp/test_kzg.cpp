@@ -92,12 +92,15 @@ static void string_case(const kzg::Fr& tau, const std::string& name, const std::
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::cerr << "usage: test_kzg <curve> <tau hex> <blob dir>" << std::endl;
+    std::cerr << "usage: test_kzg <curve> <tau hex> <blob dir> [scratch dir]" << std::endl;
     return 2;
   }
   kzg::init(atoi(argv[1]));
   const kzg::Fr tau = fr_from_hex(argv[2]);
   const std::string dir = argv[3];
+  // where the export_setup round trip writes its file (the caller's own
+  // scratch directory: a fixed name in a shared /tmp may belong to someone else)
+  const std::string scratch = argc > 4 ? argv[4] : "/tmp";
 
   // device selector (extension): explicit device 0 is the default; a
   // negative ordinal is an argument error
@@ -329,7 +332,7 @@ int main(int argc, char** argv) {
   // export_setup -> trusted_setup(filename) round trip (trusted_setup.cpp:76-121, 256-287)
   {
     kzg::trusted_setup kzg(40, tau);
-    const std::string path = "/tmp/kzgx_setup_" + std::to_string(kzg::curve()) + ".bin";
+    const std::string path = scratch + "/kzgx_setup_" + std::to_string(kzg::curve()) + ".bin";
     kzg.export_setup(path);
     kzg::trusted_setup loaded(path);
     check_test(loaded.size() == 40, "export/load, size");

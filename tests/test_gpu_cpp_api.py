@@ -17,12 +17,13 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 
 @pytest.mark.parametrize("curve_id,name", [(0, "BN254"), (1, "BLS12381")])
-def test_cpp_api_against_golden(curve_id, name):
+def test_cpp_api_against_golden(curve_id, name, tmp_path):
     assert os.path.exists(BIN), "run __graft_entry__.build()"
     with open(os.path.join(GOLD, name + ".json")) as f:
         g = json.load(f)
     C = K.CURVES[name]
-    res = subprocess.run([BIN, str(curve_id), g["tau"], GOLD], capture_output=True, text=True, timeout=600)
+    res = subprocess.run([BIN, str(curve_id), g["tau"], GOLD, str(tmp_path)], capture_output=True, text=True,
+                         timeout=600)
     out = res.stdout.splitlines()
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
     assert not [l for l in out if l.startswith("FAILED")]

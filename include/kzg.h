@@ -182,6 +182,18 @@ class trusted_setup {
    *  result k == verify_proof(commits[k], proofs[k], blob {points[k]}). */
   std::vector<bool> verify_proofs(std::vector<commit>& commits, std::vector<proof>& proofs,
                                   const std::vector<std::pair<Fr, Fr>>& points);
+  /** Extension: one pairing check for all openings (kzgx_verify_aggregate
+   *  with library-drawn 128-bit challenges); true iff every (commits[k],
+   *  proofs[k], points[k]) verifies (false-accept probability <= 2^-128).
+   *  On false, verify_proofs() says which.  An empty batch is true.
+   *  @throws std::invalid_argument on mismatched sizes */
+  bool verify_proofs_aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
+                                const std::vector<std::pair<Fr, Fr>>& points);
+  /** Extension: sum scalars[k] * points[k] on the GPU (kzgx_msm_g1_points).
+   *  KZG commitments are additively homomorphic: the combination of
+   *  commitments is the commitment of the combined polynomials.
+   *  @throws std::invalid_argument on mismatched sizes */
+  G1 linear_combination(const std::vector<G1>& points, const std::vector<Fr>& scalars);
   /** copy of the G1 / G2 SRS points */
   std::vector<G1> g1_points() const;
   std::vector<G2> g2_points() const;

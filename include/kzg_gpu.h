@@ -323,6 +323,57 @@ int kzgx_verify_single_batch_device(kzgx_ctx* ctx, const void* d_commits, const 
  * Both give the same booleans; 0 forces the lane-per-opening kernel. */
 int kzgx_set_verify_wave_max(kzgx_ctx* ctx, size_t max_count);
 
+/* ---- variable-base G1 MSM and aggregated verification (extensions) ---------- */
+/* out = sum_{k<n} scalars[k] * points[k] over caller-supplied points: n
+ * canonical affine points (x || y, all-zero = infinity; is_inf optional
+ * flags, nonzero = infinity) and n canonical scalars (4 x uint64, < r).  No
+ * SRS is needed.  n == 0 gives infinity.  Points may repeat and may be each
+ * other's negatives.  Every step is an exact group operation: the affine
+ * result is bit-exact with any other correct evaluation.  At most
+ * KZGX_MSM_POINTS_MAX points per call, else KZGX_ERR_ARG.  KZG commitments
+ * are additively homomorphic, so this is also a linear combination of
+ * commitments.  Points are taken as canonical and on the curve (not checked). */
+#define KZGX_MSM_POINTS_MAX ((size_t)1 << 22)
+int kzgx_msm_g1_points(kzgx_ctx* ctx, const uint64_t* points_xy, const int* is_inf, const uint64_t* scalars, size_t n,
+                       uint64_t* out_xy, int* out_is_inf);
+/* device pointers, enqueued on stream (NULL = the context's): d_is_inf n x
+ * uint32 (may be NULL), d_out_xy one point, d_out_is_inf one uint32 */
+int kzgx_msm_g1_points_device(kzgx_ctx* ctx, const void* d_points_xy, const void* d_is_inf, const void* d_scalars,
+                              size_t n, void* d_out_xy, void* d_out_is_inf, void* stream);
+/* Aggregated check of count single-point openings with challenges r_k:
+ *   *ok = e(sum r_k proof_k, [tau]G2) == e(sum r_k (commit_k - [y_k]G + [z_k] proof_k), G2)
+ * -- two variable-base MSMs (over the proofs; over commits, proofs and G1[0]
+ * with the scalars r_k, r_k z_k and -sum r_k y_k) and ONE two-pairing product,
+ * instead of one product per opening.
+ *  SRS: needs G1[0] = G and G2[0..1] as kzgx_verify_single_batch does, else
+ *   KZGX_ERR_NO_SRS.
+ *  challenges: count x 4 uint64 canonical scalars.  NULL (host entry only):
+ *   the library draws independent 128-bit values from std::random_device (as
+ *   the reference draws tau), r_0 = 1.  NULL on the device entry is
+ *   KZGX_ERR_ARG.  count == 0 gives *ok = 1; at most KZGX_MSM_POINTS_MAX / 2
+ *   - 1 openings per call, else KZGX_ERR_ARG.
+ *  Points are taken as canonical and on the curve, exactly as
+ *   kzgx_verify_single_batch takes them (the C++ facade's deserialize
+ *   validates).  Subgroup membership is NOT checked on BLS12-381: a caller
+ *   who needs it must check before aggregating -- components outside the
+ *   prime-order subgroup are the known weakness of random-combination checks.
+ *  Equivalence: with explicit challenges the answer is a deterministic
+ *   function of the inputs (the equation above, nothing else).  It equals the
+ *   AND of the per-opening verifies when every opening is valid, and whenever
+ *   exactly one opening is invalid and every challenge is nonzero.  Several
+ *   invalid openings can cancel for particular challenges (two errors +d and
+ *   -d under equal challenges pass), so challenges the prover can predict
+ *   prove nothing; with unpredictable 128-bit challenges the probability of a
+ *   difference from the AND is <= 2^-128. */
+int kzgx_verify_aggregate(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, const uint64_t* proofs_xy,
+                          const int* proof_inf, const uint64_t* zs, const uint64_t* ys, const uint64_t* challenges,
+                          size_t count, int* ok);
+/* device pointers (inf flags uint32, may be NULL), d_ok: one uint32;
+ * asynchronous on stream (NULL = the context's) */
+int kzgx_verify_aggregate_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, const void* d_proofs,
+                                 const void* d_proof_inf, const void* d_z, const void* d_y, const void* d_challenges,
+                                 size_t count, void* d_ok, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

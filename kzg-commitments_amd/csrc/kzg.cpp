@@ -613,6 +613,54 @@ std::vector<bool> trusted_setup::verify_proofs(std::vector<commit>& commits, std
   return res;
 }
 
+bool trusted_setup::verify_proofs_aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
+                                             const std::vector<std::pair<Fr, Fr>>& points) {
+  const size_t m = commits.size();
+  if (proofs.size() != m || points.size() != m)
+    throw std::invalid_argument("verify_proofs_aggregated: size mismatch");
+  if (m == 0) return true;
+  const int nl = base_limbs();
+  std::vector<uint64_t> c(2 * nl * m, 0), p(2 * nl * m, 0), z(4 * m), y(4 * m);
+  std::vector<int> ci(m), pi(m);
+  for (size_t k = 0; k < m; k++) {
+    const G1& cg = commits[k].get_curve_point();
+    const G1& pg = proofs[k].get_curve_point();
+    for (int i = 0; i < nl; i++) {
+      c[2 * nl * k + i] = cg.x[i];
+      c[2 * nl * k + nl + i] = cg.y[i];
+      p[2 * nl * k + i] = pg.x[i];
+      p[2 * nl * k + nl + i] = pg.y[i];
+    }
+    ci[k] = cg.inf;
+    pi[k] = pg.inf;
+    std::memcpy(&z[4 * k], points[k].first.v.data(), 32);
+    std::memcpy(&y[4 * k], points[k].second.v.data(), 32);
+  }
+  int ok = 0;
+  check(kzgx_verify_aggregate(ctx, c.data(), ci.data(), p.data(), pi.data(), z.data(), y.data(), nullptr, m, &ok),
+        "kzgx_verify_aggregate");
+  return ok != 0;
+}
+
+G1 trusted_setup::linear_combination(const std::vector<G1>& points, const std::vector<Fr>& scalars) {
+  const size_t m = points.size();
+  if (scalars.size() != m) throw std::invalid_argument("linear_combination: size mismatch");
+  const int nl = base_limbs();
+  std::vector<uint64_t> xy(2 * nl * m + 1, 0), s(4 * m + 1), out(2 * nl);
+  std::vector<int> inf(m + 1);
+  for (size_t k = 0; k < m; k++) {
+    for (int i = 0; i < nl; i++) {
+      xy[2 * nl * k + i] = points[k].x[i];
+      xy[2 * nl * k + nl + i] = points[k].y[i];
+    }
+    inf[k] = points[k].inf;
+    std::memcpy(&s[4 * k], scalars[k].v.data(), 32);
+  }
+  int oi = 1;
+  check(kzgx_msm_g1_points(ctx, xy.data(), inf.data(), s.data(), m, out.data(), &oi), "kzgx_msm_g1_points");
+  return to_g1(out.data(), oi != 0);
+}
+
 std::vector<G1> trusted_setup::g1_points() const {
   const int nl = base_limbs();
   std::vector<uint64_t> xy(2 * nl * n);

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <random>
 #include <string>
 #include <vector>
 
@@ -581,7 +582,7 @@ void kzgx_destroy(kzgx_ctx* ctx) {
   for (auto& w : c.ws) {
     void* wb[] = {w.counts, w.offsets, w.cursors, w.entries, w.bsum,  w.heads,
                   w.tails,  w.tailk,   w.rt,      w.q,       w.parts, w.fpart, w.fsum, w.gpart, w.gmeta, w.sstate, w.qbig,
-                  w.lat_cnt};
+                  w.lat_cnt, w.var_tab, w.var_parts, w.var_scal, w.var_pt, w.var_inf};
     for (void* p : wb)
       if (p) (void)hipFree(p);
     if (w.done) (void)hipEventDestroy(w.done);
@@ -1579,6 +1580,139 @@ int kzgx_verify_single_batch(kzgx_ctx* ctx, const uint64_t* commits_xy, const in
   KZGX_TRY_HIP(hipMemcpyAsync(v.data(), d_ok, count * 4, hipMemcpyDeviceToHost, st));
   KZGX_TRY_HIP(hipStreamSynchronize(st));
   for (size_t k = 0; k < count; k++) ok[k] = (int)v[k];
+  return KZGX_OK;
+}
+
+// ---- variable-base MSM over caller points, aggregated verification ---------
+int kzgx_msm_g1_points_device(kzgx_ctx* ctx, const void* d_points_xy, const void* d_is_inf, const void* d_scalars,
+                              size_t n, void* d_out_xy, void* d_out_is_inf, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (!d_out_xy || !d_out_is_inf || (n > 0 && (!d_points_xy || !d_scalars)) || n > KZGX_MSM_POINTS_MAX)
+    return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const kzgx::PointSeg seg{(const uint32_t*)d_points_xy, (const uint32_t*)d_is_inf, n};
+  return kzgx::msm_points(&ctx->c, *ws, &seg, 1, (const uint32_t*)d_scalars, (uint32_t*)d_out_xy,
+                          (uint32_t*)d_out_is_inf, st);
+}
+
+int kzgx_msm_g1_points(kzgx_ctx* ctx, const uint64_t* points_xy, const int* is_inf, const uint64_t* scalars, size_t n,
+                       uint64_t* out_xy, int* out_is_inf) {
+  KZGX_TRY(activate(ctx));
+  if (!out_xy || !out_is_inf || (n > 0 && (!points_xy || !scalars)) || n > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  const size_t pb = point_words(ctx) * 4;
+  void *d_p, *d_f, *d_s, *d_o;
+  KZGX_TRY(stage(ctx, 0, n * pb + 16, &d_p));
+  KZGX_TRY(stage(ctx, 1, n * 4 + 16, &d_f));
+  KZGX_TRY(stage(ctx, 2, n * 32 + 16, &d_s));
+  KZGX_TRY(stage(ctx, 3, pb + 16, &d_o));
+  hipStream_t st = ctx->c.stream;
+  std::vector<uint32_t> f(n);
+  for (size_t i = 0; i < n; i++) f[i] = is_inf ? (uint32_t)(is_inf[i] != 0) : 0u;
+  if (n) {
+    KZGX_TRY_HIP(hipMemcpyAsync(d_p, points_xy, n * pb, hipMemcpyHostToDevice, st));
+    KZGX_TRY_HIP(hipMemcpyAsync(d_f, f.data(), n * 4, hipMemcpyHostToDevice, st));
+    KZGX_TRY_HIP(hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st));
+  }
+  uint32_t* d_oi = (uint32_t*)((char*)d_o + pb);
+  KZGX_TRY(kzgx_msm_g1_points_device(ctx, d_p, d_f, d_s, n, d_o, d_oi, nullptr));
+  uint32_t oi = 0;
+  KZGX_TRY_HIP(hipMemcpyAsync(out_xy, d_o, pb, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(&oi, d_oi, 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  *out_is_inf = (int)oi;
+  return KZGX_OK;
+}
+
+int kzgx_verify_aggregate_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, const void* d_proofs,
+                                 const void* d_proof_inf, const void* d_z, const void* d_y, const void* d_challenges,
+                                 size_t count, void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (!d_ok || !d_challenges) return KZGX_ERR_ARG;
+  if (count > 0 && (!d_commits || !d_proofs || !d_z || !d_y)) return KZGX_ERR_ARG;
+  if (2 * count + 1 > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0 || ctx->n_srs2 < 2) return KZGX_ERR_NO_SRS;
+  hipStream_t st = pick(ctx, stream);
+  if (count == 0) {
+    KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)d_ok, 1, 1, st));
+    return KZGX_OK;
+  }
+  kzgx::Ctx* c = &ctx->c;
+  kzgx::WsLease ws = c->ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const size_t pw = point_words(ctx);
+  // scalars r | r z | t (+ the block sums' scratch); A | B | their flags | z = y = 0
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->var_scal, (2 * count + 1 + 256) * 32, &ws->var_scal_b));
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->var_pt, (2 * pw + 4 + 16) * 4, &ws->var_pt_b));
+  uint32_t* A = ws->var_pt;
+  uint32_t* B = A + pw;
+  uint32_t* fl = B + pw;  // [A_inf, B_inf, -, -]
+  uint32_t* zero = fl + 4;
+  KZGX_TRY_HIP(hipMemsetAsync(zero, 0, 64, st));
+  KZGX_TRY(kzgx::aggregate_scalars(c, (const uint32_t*)d_z, (const uint32_t*)d_y, (const uint32_t*)d_challenges, count,
+                                   ws->var_scal, st));
+  // A = sum r_k proof_k
+  const kzgx::PointSeg sa{(const uint32_t*)d_proofs, (const uint32_t*)d_proof_inf, count};
+  KZGX_TRY(kzgx::msm_points(c, *ws, &sa, 1, (const uint32_t*)d_challenges, A, fl, st));
+  // B = sum r_k commit_k + sum r_k z_k proof_k - (sum r_k y_k) G1[0]
+  const kzgx::PointSeg sb[3] = {{(const uint32_t*)d_commits, (const uint32_t*)d_commit_inf, count},
+                                {(const uint32_t*)d_proofs, (const uint32_t*)d_proof_inf, count},
+                                {ctx->d_srs_canon, nullptr, 1}};
+  KZGX_TRY(kzgx::msm_points(c, *ws, sb, 3, ws->var_scal, B, fl + 1, st));
+  // e(A, [tau]G2) == e(B, G2[0]): the single-opening check of proof = A,
+  // commit = B at z = 0, y = 0
+  return kzgx_verify_single_batch_device(ctx, B, fl + 1, A, fl, zero, zero + 8, 1, d_ok, stream);
+}
+
+int kzgx_verify_aggregate(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, const uint64_t* proofs_xy,
+                          const int* proof_inf, const uint64_t* zs, const uint64_t* ys, const uint64_t* challenges,
+                          size_t count, int* ok) {
+  KZGX_TRY(activate(ctx));
+  if (!ok) return KZGX_ERR_ARG;
+  if (count > 0 && (!commits_xy || !proofs_xy || !zs || !ys)) return KZGX_ERR_ARG;
+  if (2 * count + 1 > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0 || ctx->n_srs2 < 2) return KZGX_ERR_NO_SRS;
+  if (count == 0) {
+    *ok = 1;
+    return KZGX_OK;
+  }
+  // library-drawn challenges: independent 128-bit values, r_0 = 1
+  std::vector<uint64_t> drawn;
+  if (!challenges) {
+    drawn.assign(count * 4, 0);
+    std::random_device rd;
+    for (size_t k = 0; k < count; k++)
+      for (int j = 0; j < 2; j++) drawn[4 * k + j] = ((uint64_t)rd() << 32) | (uint64_t)rd();
+    drawn[0] = 1;
+    drawn[1] = 0;
+    challenges = drawn.data();
+  }
+  const size_t pb = point_words(ctx) * 4;
+  void *d_c, *d_p, *d_s, *d_f;
+  KZGX_TRY(stage(ctx, 0, count * pb, &d_c));
+  KZGX_TRY(stage(ctx, 1, count * pb, &d_p));
+  KZGX_TRY(stage(ctx, 2, count * 96, &d_s));
+  KZGX_TRY(stage(ctx, 3, count * 8 + 16, &d_f));
+  std::vector<uint32_t> fl(2 * count);
+  for (size_t k = 0; k < count; k++) {
+    fl[k] = commit_inf ? (uint32_t)(commit_inf[k] != 0) : 0u;
+    fl[count + k] = proof_inf ? (uint32_t)(proof_inf[k] != 0) : 0u;
+  }
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_c, commits_xy, count * pb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_p, proofs_xy, count * pb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_s, zs, count * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync((char*)d_s + count * 32, ys, count * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync((char*)d_s + count * 64, challenges, count * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_f, fl.data(), count * 8, hipMemcpyHostToDevice, st));
+  uint32_t* d_ok = (uint32_t*)d_f + 2 * count;
+  KZGX_TRY(kzgx_verify_aggregate_device(ctx, d_c, d_f, d_p, (uint32_t*)d_f + count, d_s, (char*)d_s + count * 32,
+                                        (char*)d_s + count * 64, count, d_ok, nullptr));
+  uint32_t v = 0;
+  KZGX_TRY_HIP(hipMemcpyAsync(&v, d_ok, 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  *ok = v ? 1 : 0;
   return KZGX_OK;
 }
 

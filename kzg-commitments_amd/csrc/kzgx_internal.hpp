@@ -41,6 +41,12 @@ struct MsmWs {
   uint32_t *bsum = nullptr, *heads = nullptr, *tails = nullptr, *tailk = nullptr, *rt = nullptr, *q = nullptr,
            *parts = nullptr, *fpart = nullptr, *fsum = nullptr, *gpart = nullptr, *gmeta = nullptr, *qbig = nullptr;
   uint8_t* sstate = nullptr;
+  // variable-base MSM over caller points (msm.hip msm_points): the points in
+  // Montgomery form, their infinity flags, the per-(chunk, window) XYZZ sums;
+  // verify_aggregate's scalars (r | r z | -sum r y) and its two MSM results
+  uint32_t *var_tab = nullptr, *var_parts = nullptr, *var_scal = nullptr, *var_pt = nullptr;
+  uint8_t* var_inf = nullptr;
+  size_t var_tab_b = 0, var_parts_b = 0, var_scal_b = 0, var_pt_b = 0, var_inf_b = 0;
   uint32_t* lat_cnt = nullptr;  // [64] arrival counters of the one-launch latency path (msm_fixed.hip)
   size_t counts_b = 0, offsets_b = 0, cursors_b = 0, entries_b = 0, bsum_b = 0, heads_b = 0, tails_b = 0, tailk_b = 0,
          rt_b = 0, q_b = 0, parts_b = 0, fpart_b = 0, fsum_b = 0, gpart_b = 0, gmeta_b = 0, sstate_b = 0, qbig_b = 0;
@@ -288,6 +294,21 @@ int debug_latency(Ctx* ctx, int op, uint32_t iters, double* res);  // ns, core c
 int xyzz_sum(Ctx* ctx, const uint32_t* d_parts, size_t count, uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st);
 int msm_batch(Ctx* ctx, const uint32_t* d_scalars, size_t n, size_t batch, size_t stride_words, uint32_t* d_out,
               uint32_t* d_out_inf, hipStream_t st);
+// variable-base MSM (msm.hip): out = sum_k s_k P_k over the concatenation of
+// nseg arrays of canonical affine points (inf: uint32 flags or null); the
+// total scalars are contiguous in d_scalars.  ws: the caller's lease on st.
+struct PointSeg {
+  const uint32_t* xy;
+  const uint32_t* inf;
+  size_t n;
+};
+constexpr size_t MSM_POINTS_MAX = KZGX_MSM_POINTS_MAX;
+int msm_points(Ctx* ctx, MsmWs& ws, const PointSeg* segs, int nseg, const uint32_t* d_scalars, uint32_t* d_out,
+               uint32_t* d_out_inf, hipStream_t st);
+// verify_aggregate's scalars (poly.hip): d_out = r_0..r_{n-1} | r_k z_k | -sum r_k y_k  (2 n + 1 scalars,
+// followed by 256 scalars of scratch for the block sums)
+int aggregate_scalars(Ctx* ctx, const uint32_t* d_z, const uint32_t* d_y, const uint32_t* d_r, size_t n,
+                      uint32_t* d_out, hipStream_t st);
 // one MSM as an XYZZ record, no affine conversion (msm.hip)
 int msm_partial_xyzz(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t* d_rec, hipStream_t st);
 int gen_srs_points(Ctx* ctx, const uint32_t* tau_canon_host, size_t start, size_t n, uint32_t* d_out_canon,

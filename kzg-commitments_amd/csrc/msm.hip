@@ -1683,6 +1683,312 @@ static int msm_big(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t* d_ou
   }
 }
 
+// --------------------------------------------------------------------------
+// variable-base MSM over caller points (kzgx_msm_g1_points)
+// --------------------------------------------------------------------------
+// out = sum_k s_k P_k with no table of doublings: window w of every scalar
+// goes to its OWN bucket set, so an MSM of n points with W windows is a batch
+// of W bucket sets over one point table (the caller's points, converted to
+// Montgomery form once per call).  n is cut into chunks of VAR_CHUNK points
+// (the one-workgroup scan, as msm_single_chunked), so the batch is
+// chunks x W bucket sets of at most VAR_CHUNK entries each: set b = ch W + w
+// holds digit w of the scalars of chunk ch.  Count / scatter below emit one
+// digit per (point, window); accumulation, segment merge and the bucket
+// running sums are the batched Pippenger's kernels.  k_var_horner then sums
+// the chunks of every window and folds sum_w 2^(c w) S_w by Horner's rule
+// (c doublings a step, XYZZ, one affine conversion).  A window whose digits
+// are all zero (the upper half for 128-bit scalars) has no entries: its
+// accumulation threads exit, and Horner does not double an infinite prefix.
+// Points repeat (one commitment opened at many points): the bucket additions
+// are curve.hpp's complete formulas, P + P and P + (-P) included.
+constexpr uint32_t VAR_SPT = 16;             // points per thread in count / scatter
+constexpr uint32_t VAR_BLK = 256 * VAR_SPT;  // points per count block: one digit per point, so a block needs
+                                             // this many to outweigh its 2^(c-1)-counter histogram row
+constexpr size_t VAR_CHUNK = (size_t)1 << 17;
+constexpr int VAR_MAX_W = Win<10>::W;
+
+// caller points (canonical affine, optional uint32 infinity flags) -> Montgomery
+template <class C>
+__global__ void k_var_to_mont(const uint32_t* __restrict__ canon, const uint32_t* __restrict__ flags,
+                              uint32_t* __restrict__ table, uint8_t* __restrict__ inf, uint32_t n) {
+  constexpr int AW = affine_words<C>();
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Affine<C> a;
+  bool finite = affine_from_canonical<C>(canon + (size_t)i * 2 * C::Fp::N, a);
+  if (flags && flags[i]) finite = false;
+  inf[i] = finite ? 0 : 1;
+  affine_store<C>(table + (size_t)i * AW, a);
+}
+
+// signed digit w of a scalar (the recoding's carry chain runs from window 0)
+template <int CB>
+KZGX_DEV int var_digit(const uint32_t (&s)[8], int w) {
+  uint32_t carry = 0;
+  int mine = 0;
+#pragma unroll
+  for (int v = 0; v < Win<CB>::W; v++) {
+    const int d = digit_at<CB>(s, v, carry);
+    if (v == w) mine = d;
+  }
+  return mine;
+}
+
+// bucket histogram of every (bucket set, count block); layout as k_msm_count
+template <int CB>
+__global__ __launch_bounds__(256) void k_var_count(const uint32_t* __restrict__ scalars, uint32_t n, uint32_t L,
+                                                   const uint8_t* __restrict__ inf, uint32_t* __restrict__ bcount,
+                                                   uint32_t nblk) {
+  constexpr int W = Win<CB>::W;
+  constexpr uint32_t NB = Win<CB>::NB;
+  __shared__ uint32_t hist[NB];
+  const uint32_t b = blockIdx.y, ch = b / W;
+  const int w = (int)(b % W);
+  for (uint32_t k = threadIdx.x; k < NB; k += 256) hist[k] = 0;
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t j = 0; j < VAR_SPT; j++) {
+    const uint32_t li = blockIdx.x * VAR_BLK + j * 256 + threadIdx.x;
+    const uint32_t gi = ch * L + li;
+    if (li < L && gi < n && !inf[gi]) {
+      uint32_t s[8];
+      load_scalar(scalars + (size_t)gi * 8, s);
+      const int d = var_digit<CB>(s, w);
+      if (d != 0) atomicAdd(&hist[(d < 0 ? -d : d) - 1], 1u);
+    }
+  }
+  __syncthreads();
+  uint32_t* out = bcount + ((size_t)b * nblk + blockIdx.x) * NB;
+  for (uint32_t k = threadIdx.x; k < NB; k += 256) out[k] = hist[k];
+}
+
+// (point index | sign) entries of bucket set b into bucket order: the block
+// sorts its digits in LDS, then writes runs (as k_msm_scatter)
+template <int CB>
+__global__ __launch_bounds__(256) void k_var_scatter(const uint32_t* __restrict__ scalars, uint32_t n, uint32_t L,
+                                                     const uint8_t* __restrict__ inf,
+                                                     const uint32_t* __restrict__ bcount,
+                                                     const uint32_t* __restrict__ bbase, uint32_t nblk,
+                                                     uint32_t* __restrict__ entries) {
+  constexpr int W = Win<CB>::W;
+  constexpr uint32_t NB = Win<CB>::NB;
+  constexpr uint32_t PER = NB / 256;
+  __shared__ uint32_t stage[VAR_BLK];
+  __shared__ uint32_t lstart[NB + 1];
+  __shared__ uint32_t cur[NB];
+  __shared__ uint32_t part[256];
+  const uint32_t b = blockIdx.y, ch = b / W;
+  const int w = (int)(b % W);
+  const uint32_t t = threadIdx.x;
+  const size_t hb = ((size_t)b * nblk + blockIdx.x) * NB;
+  uint32_t local = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < PER; j++) {
+    const uint32_t c = bcount[hb + t * PER + j];
+    cur[t * PER + j] = c;
+    local += c;
+  }
+  part[t] = local;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256; d <<= 1) {
+    uint32_t v = (t >= d) ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[t] - local;
+#pragma unroll
+  for (uint32_t j = 0; j < PER; j++) {
+    const uint32_t c = cur[t * PER + j];
+    lstart[t * PER + j] = run;
+    cur[t * PER + j] = run;
+    run += c;
+  }
+  if (t == 255) lstart[NB] = run;
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t j = 0; j < VAR_SPT; j++) {
+    const uint32_t li = blockIdx.x * VAR_BLK + j * 256 + t;
+    const uint32_t gi = ch * L + li;
+    if (li < L && gi < n && !inf[gi]) {
+      uint32_t s[8];
+      load_scalar(scalars + (size_t)gi * 8, s);
+      const int d = var_digit<CB>(s, w);
+      if (d != 0) {
+        const uint32_t pos = atomicAdd(&cur[(d < 0 ? -d : d) - 1], 1u);  // < lstart[NB] <= VAR_BLK
+        stage[pos] = gi | (d < 0 ? 0x80000000u : 0u);
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t k = t; k < NB; k += 256) cur[k] = bbase[hb + k];  // global write bases
+  __syncthreads();
+  uint32_t* out = entries + (size_t)b * L;
+  const uint32_t total = lstart[NB];
+  for (uint32_t j = t; j < total; j += 256) {
+    uint32_t lo = 0, hi = NB;  // bucket of position j: lstart[lo] <= j < lstart[hi]
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (lstart[mid] <= j)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    out[cur[lo] + (j - lstart[lo])] = stage[j];
+  }
+}
+
+// parts[ch W + w]: the XYZZ sum of window w of chunk ch.  Thread w sums its
+// window over the chunks; thread 0 then folds sum_w 2^(c w) S_w from the top
+// window down and converts once.  chunks == 0 gives infinity.
+template <class C>
+__global__ __launch_bounds__(64) void k_var_horner(const uint32_t* __restrict__ parts, uint32_t chunks, int W, int c,
+                                                   uint32_t* __restrict__ out, uint32_t* __restrict__ out_inf) {
+  constexpr int XW = xyzz_words<C>();
+  __shared__ uint32_t lds[VAR_MAX_W * XW];
+  const int t = (int)threadIdx.x;
+  if (t < W) {
+    Xyzz<C> acc = xyzz_inf<C>();
+    for (uint32_t ch = 0; ch < chunks; ch++) acc = xyzz_add<C>(acc, xyzz_load<C>(parts + ((size_t)ch * W + t) * XW));
+    xyzz_store<C>(lds + t * XW, acc);
+  }
+  __syncthreads();
+  if (t != 0) return;
+  Xyzz<C> acc = xyzz_load<C>(lds + (W - 1) * XW);
+#pragma unroll 1
+  for (int w = W - 2; w >= 0; w--) {
+    if (!xyzz_is_inf<C>(acc)) {
+#pragma unroll 1
+      for (int s = 0; s < c; s++) acc = xyzz_dbl<C>(acc);
+    }
+    acc = xyzz_add<C>(acc, xyzz_load<C>(lds + w * XW));
+  }
+  constexpr int N = C::Fp::N;
+  uint32_t wx[N], wy[N];
+  const bool fin = xyzz_to_canonical_lane<C>(acc, wx, wy);
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    out[k] = wx[k];
+    out[N + k] = wy[k];
+  }
+  *out_inf = fin ? 0u : 1u;
+}
+
+// The window for chunks of L points: the smallest modelled cost
+// W(c) (L + 3 2^(c-1)) -- L mixed additions per window against a bucket
+// reduction of 2 full additions (~1.5 mixed ones each) per bucket -- over the
+// windows the batched kernels are built for.  KZGX_VAR_WINDOW pins it (A/B).
+static int var_window_bits(size_t L) {
+  static const int pin = std::getenv("KZGX_VAR_WINDOW") ? std::atoi(std::getenv("KZGX_VAR_WINDOW")) : 0;
+  if (pin >= 10 && pin <= 13) return pin;
+  int best = 10;
+  size_t best_cost = ~(size_t)0;
+  for (int c = 10; c <= 13; c++) {
+    const size_t cost = (size_t)((257 + c - 1) / c) * (L + 3 * ((size_t)1 << (c - 1)));
+    if (cost < best_cost) {
+      best_cost = cost;
+      best = c;
+    }
+  }
+  return best;
+}
+
+// the chunks x W window sums of n table points into ws.var_parts
+template <class C, int CB>
+static int msm_points_impl(Ctx* ctx, MsmWs& ws, const uint32_t* d_scalars, size_t n, size_t L, size_t chunks,
+                           hipStream_t st) {
+  constexpr int W = Win<CB>::W;
+  constexpr uint32_t NB = Win<CB>::NB;
+  const size_t batch = chunks * W;
+  const size_t emax = L;  // one digit per (point, window)
+  uint32_t K = ctx->seg_k;
+  while (K > 8 && batch * emax / K < 131072) K >>= 1;
+  const size_t smax = (emax + K - 1) / K;
+  const size_t nwg = (smax + ACC_WG - 1) / ACC_WG;
+  const size_t nblk = (L + VAR_BLK - 1) / VAR_BLK;
+  const size_t XB = xyzz_words<C>() * sizeof(uint32_t);
+  if (batch > 65535 || nblk > 65535 || nwg > 65535) return KZGX_ERR_ARG;  // grid limits
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.counts, batch * nblk * NB * 4, &ws.counts_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.cursors, batch * nblk * NB * 4, &ws.cursors_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.offsets, batch * (NB + 1) * 4, &ws.offsets_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.entries, batch * emax * 4, &ws.entries_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.bsum, batch * NB * XB, &ws.bsum_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.heads, batch * smax * XB, &ws.heads_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.tails, batch * smax * XB, &ws.tails_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.tailk, batch * smax * 4, &ws.tailk_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.sstate, batch * smax, &ws.sstate_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.gpart, batch * nwg * 2 * XB, &ws.gpart_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.gmeta, batch * nwg * 2 * 4, &ws.gmeta_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.rt, batch * (NB / RED_J) * 2 * XB, &ws.rt_b));
+  uint32_t* ghead = ws.gpart;
+  uint32_t* gtail = ws.gpart + batch * nwg * xyzz_words<C>();
+  uint32_t* gtailk = ws.gmeta;
+  uint32_t* gflag = ws.gmeta + batch * nwg;
+  dim3 blk(256);
+  dim3 gs((unsigned)nblk, (unsigned)batch);
+  {
+    ProfScope p(ctx, st, "var_sort");
+    hipLaunchKernelGGL(k_var_count<CB>, gs, blk, 0, st, d_scalars, (uint32_t)n, (uint32_t)L, ws.var_inf, ws.counts,
+                       (uint32_t)nblk);
+    hipLaunchKernelGGL(k_msm_scan<CB>, dim3((unsigned)batch), blk, 0, st, ws.counts, (uint32_t)nblk, ws.offsets,
+                       ws.cursors);
+    hipLaunchKernelGGL(k_var_scatter<CB>, gs, blk, 0, st, d_scalars, (uint32_t)n, (uint32_t)L, ws.var_inf, ws.counts,
+                       ws.cursors, (uint32_t)nblk, ws.entries);
+  }
+  {
+    ProfScope p(ctx, st, "var_accum");
+    hipLaunchKernelGGL(k_msm_accum<C>, dim3((unsigned)((smax + 255) / 256), (unsigned)batch), blk, 0, st, ws.entries,
+                       emax, ws.offsets, NB, ws.var_tab, K, (uint32_t)smax, ws.bsum, ws.heads, ws.tails, ws.tailk,
+                       ws.sstate);
+  }
+  ProfScope p(ctx, st, "var_reduce");
+  hipLaunchKernelGGL(k_msm_merge<C>, dim3((unsigned)nwg, (unsigned)batch), dim3(ACC_WG), 0, st, ws.heads, ws.tails,
+                     ws.tailk, ws.sstate, (uint32_t)smax, NB, (uint32_t)nwg, ws.bsum, ghead, gtail, gtailk, gflag);
+  hipLaunchKernelGGL(k_msm_wg_fixup<C>, dim3((unsigned)((nwg + 63) / 64), (unsigned)batch), dim3(64), 0, st, NB,
+                     (uint32_t)nwg, ghead, gtail, gtailk, gflag, ws.bsum);
+  KZGX_TRY_HIP(hipGetLastError());
+  return bucket_reduce<C, NB, RED_J>(ctx, ws, batch, st, nullptr, nullptr, ws.var_parts);
+}
+
+template <class C>
+static int msm_points_c(Ctx* ctx, MsmWs& ws, const PointSeg* segs, int nseg, const uint32_t* d_scalars,
+                        uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st) {
+  constexpr size_t PWB = affine_words<C>() * sizeof(uint32_t);
+  const size_t XB = xyzz_words<C>() * sizeof(uint32_t);
+  size_t n = 0;
+  for (int k = 0; k < nseg; k++) n += segs[k].n;
+  if (n > MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  const size_t L = n < VAR_CHUNK ? n : VAR_CHUNK;
+  const size_t chunks = n ? (n + L - 1) / L : 0;
+  const int c = var_window_bits(L);
+  const int W = (257 + c - 1) / c;
+  if (n) {
+    KZGX_TRY(dev_alloc(ctx, (void**)&ws.var_tab, n * PWB, &ws.var_tab_b));
+    KZGX_TRY(dev_alloc(ctx, (void**)&ws.var_inf, n, &ws.var_inf_b));
+    KZGX_TRY(dev_alloc(ctx, (void**)&ws.var_parts, chunks * W * XB, &ws.var_parts_b));
+    size_t at = 0;
+    for (int k = 0; k < nseg; k++) {
+      if (!segs[k].n) continue;
+      hipLaunchKernelGGL(k_var_to_mont<C>, dim3((unsigned)((segs[k].n + 255) / 256)), dim3(256), 0, st, segs[k].xy,
+                         segs[k].inf, ws.var_tab + at * affine_words<C>(), ws.var_inf + at, (uint32_t)segs[k].n);
+      at += segs[k].n;
+    }
+    KZGX_TRY_HIP(hipGetLastError());
+    switch (c) {
+      case 10: KZGX_TRY((msm_points_impl<C, 10>(ctx, ws, d_scalars, n, L, chunks, st))); break;
+      case 11: KZGX_TRY((msm_points_impl<C, 11>(ctx, ws, d_scalars, n, L, chunks, st))); break;
+      case 12: KZGX_TRY((msm_points_impl<C, 12>(ctx, ws, d_scalars, n, L, chunks, st))); break;
+      case 13: KZGX_TRY((msm_points_impl<C, 13>(ctx, ws, d_scalars, n, L, chunks, st))); break;
+      default: return KZGX_ERR_INTERNAL;
+    }
+  }
+  ProfScope p(ctx, st, "var_horner");
+  hipLaunchKernelGGL(k_var_horner<C>, dim3(1), dim3(64), 0, st, ws.var_parts, (uint32_t)chunks, W, c, d_out,
+                     d_out_inf);
+  KZGX_TRY_HIP(hipGetLastError());
+  return KZGX_OK;
+}
+
 // ---- per-curve entry points ---------------------------------------------
 // This file is compiled once per curve (Makefile: build/msm.o with
 // KZGX_MSM_CURVE=BN254G1 and KZGX_MSM_MAIN, build/msm_bls.o with
@@ -1702,6 +2008,8 @@ struct MsmCurve {
   static int big(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st,
                  uint32_t* xyzz_out);
   static int xyzz_sum(const uint32_t* d_parts, size_t count, uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st);
+  static int points(Ctx* ctx, MsmWs& ws, const PointSeg* segs, int nseg, const uint32_t* d_scalars, uint32_t* d_out,
+                    uint32_t* d_out_inf, hipStream_t st);
 };
 
 template <class C>
@@ -1730,6 +2038,12 @@ int MsmCurve<C>::xyzz_sum(const uint32_t* d_parts, size_t count, uint32_t* d_out
                      d_out, d_out_inf);
   KZGX_TRY_HIP(hipGetLastError());
   return KZGX_OK;
+}
+
+template <class C>
+int MsmCurve<C>::points(Ctx* ctx, MsmWs& ws, const PointSeg* segs, int nseg, const uint32_t* d_scalars,
+                        uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st) {
+  return msm_points_c<C>(ctx, ws, segs, nseg, d_scalars, d_out, d_out_inf, st);
 }
 
 #ifndef KZGX_MSM_CURVE
@@ -1789,6 +2103,13 @@ int msm_batch(Ctx* ctx, const uint32_t* d_scalars, size_t n, size_t batch, size_
               : MsmCurve<BLS12381G1>::chunked(ctx, d_scalars, n, d_out, d_out_inf, st);
   return bn ? MsmCurve<BN254G1>::batch(ctx, d_scalars, n, batch, stride_words, d_out, d_out_inf, st)
             : MsmCurve<BLS12381G1>::batch(ctx, d_scalars, n, batch, stride_words, d_out, d_out_inf, st);
+}
+
+int msm_points(Ctx* ctx, MsmWs& ws, const PointSeg* segs, int nseg, const uint32_t* d_scalars, uint32_t* d_out,
+               uint32_t* d_out_inf, hipStream_t st) {
+  return ctx->curve == KZGX_CURVE_BN254
+             ? MsmCurve<BN254G1>::points(ctx, ws, segs, nseg, d_scalars, d_out, d_out_inf, st)
+             : MsmCurve<BLS12381G1>::points(ctx, ws, segs, nseg, d_scalars, d_out, d_out_inf, st);
 }
 
 // One MSM left projective: the XYZZ sum of sum_i s_i SRS_i in d_rec

@@ -811,6 +811,68 @@ int prove_range_poly(Ctx* ctx, const uint32_t* d_P, size_t n, const uint32_t* d_
                                         : prove_range_poly_impl<BLS12381Fr>(ctx, d_P, n, d_x, len, d_q, nq, st);
 }
 
+// --------------------------------------------------------------------------
+// aggregated verification: the scalars of its two MSMs (kzgx_verify_aggregate)
+// --------------------------------------------------------------------------
+// out = r_0..r_{n-1} | s_k = r_k z_k | t = -sum_k r_k y_k (all canonical).
+// Pass 1 (grid-stride, at most AGG_BLOCKS workgroups): r copied, s written,
+// and every workgroup's sum of r_k y_k (wave sums, then the four waves
+// through LDS) into part[block].  Pass 2: one wave adds the block sums in a
+// fixed order, negates and writes t once -- no atomics, no host round trip.
+constexpr uint32_t AGG_BLOCKS = 256;
+
+template <class FR>
+__global__ __launch_bounds__(256) void k_agg_scalars(const uint32_t* __restrict__ z, const uint32_t* __restrict__ y,
+                                                     const uint32_t* __restrict__ r, uint32_t n,
+                                                     uint32_t* __restrict__ out, uint32_t* __restrict__ part) {
+  constexpr int N = FR::N;
+  __shared__ uint32_t lds[4 * N];
+  Fe<FR> acc = fe_zero<FR>();
+  for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) {
+    const Fe<FR> rc = fe_load<FR>(r + (size_t)k * N);
+    const Fe<FR> rm = fe_to_mont<FR>(rc);
+    fe_store<FR>(out + (size_t)k * N, rc);
+    fe_store<FR>(out + ((size_t)n + k) * N, fe_mul<FR>(fe_load<FR>(z + (size_t)k * N), rm));
+    acc = fe_add<FR>(acc, fe_mul<FR>(fe_load<FR>(y + (size_t)k * N), rm));
+  }
+  acc = wave_sum<FR>(acc);
+  if ((threadIdx.x & 63) == 0) fe_store<FR>(lds + (threadIdx.x >> 6) * N, acc);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; w++) acc = fe_add<FR>(acc, fe_load<FR>(lds + w * N));
+    fe_store<FR>(part + (size_t)blockIdx.x * N, acc);
+  }
+}
+
+template <class FR>
+__global__ __launch_bounds__(64) void k_agg_total(const uint32_t* __restrict__ part, uint32_t nblocks,
+                                                  uint32_t* __restrict__ t_out) {
+  constexpr int N = FR::N;
+  Fe<FR> acc = fe_zero<FR>();
+  for (uint32_t b = threadIdx.x; b < nblocks; b += 64) acc = fe_add<FR>(acc, fe_load<FR>(part + (size_t)b * N));
+  acc = wave_sum<FR>(acc);
+  if (threadIdx.x == 0) fe_store<FR>(t_out, fe_neg<FR>(acc));
+}
+
+template <class FR>
+static int aggregate_scalars_impl(const uint32_t* d_z, const uint32_t* d_y, const uint32_t* d_r, size_t n,
+                                  uint32_t* d_out, hipStream_t st) {
+  const uint32_t nblocks = (uint32_t)((n + 255) / 256 < AGG_BLOCKS ? (n + 255) / 256 : AGG_BLOCKS);
+  uint32_t* part = d_out + (2 * n + 1) * FR::N;
+  hipLaunchKernelGGL(k_agg_scalars<FR>, dim3(nblocks), dim3(256), 0, st, d_z, d_y, d_r, (uint32_t)n, d_out, part);
+  hipLaunchKernelGGL(k_agg_total<FR>, dim3(1), dim3(64), 0, st, part, nblocks, d_out + 2 * n * FR::N);
+  KZGX_TRY_HIP(hipGetLastError());
+  return KZGX_OK;
+}
+
+// d_out: 2 n + 1 scalars followed by AGG_BLOCKS scalars of scratch
+int aggregate_scalars(Ctx* ctx, const uint32_t* d_z, const uint32_t* d_y, const uint32_t* d_r, size_t n,
+                      uint32_t* d_out, hipStream_t st) {
+  if (n == 0) return KZGX_ERR_ARG;
+  return ctx->curve == KZGX_CURVE_BN254 ? aggregate_scalars_impl<BN254Fr>(d_z, d_y, d_r, n, d_out, st)
+                                        : aggregate_scalars_impl<BLS12381Fr>(d_z, d_y, d_r, n, d_out, st);
+}
+
 }  // namespace kzgx
 
 namespace kzgx {

@@ -33,6 +33,7 @@ EXPORTS = [
     "kzgx_verify_single_batch_device", "kzgx_set_verify_wave_max", "kzgx_msm_g1_sharded",
     "kzgx_quotient_single_batch", "kzgx_shared_tables", "kzgx_release_cached_memory",
     "kzgx_partial_record_words", "kzgx_msm_g1_partial_device", "kzgx_g1_sum_partials_device",
+    "kzgx_msm_g1_points", "kzgx_msm_g1_points_device", "kzgx_verify_aggregate", "kzgx_verify_aggregate_device",
 ]
 
 _lib = None
@@ -128,6 +129,10 @@ def lib():
             "kzgx_partial_record_words": (ctypes.c_int, [ctypes.c_int]),
             "kzgx_msm_g1_partial_device": (ctypes.c_int, [vp, vp, sz, vp, vp]),
             "kzgx_g1_sum_partials_device": (ctypes.c_int, [vp, vp, sz, vp, vp]),
+            "kzgx_msm_g1_points": (ctypes.c_int, [vp, u64p, intp, u64p, sz, u64p, intp]),
+            "kzgx_msm_g1_points_device": (ctypes.c_int, [vp, vp, vp, vp, sz, vp, vp, vp]),
+            "kzgx_verify_aggregate": (ctypes.c_int, [vp, u64p, intp, u64p, intp, u64p, u64p, u64p, sz, intp]),
+            "kzgx_verify_aggregate_device": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -550,3 +555,48 @@ class Context:
                                    stream=None):
         _chk(lib().kzgx_verify_single_batch_device(self.h, d_commits, d_commit_inf, d_proofs, d_proof_inf, d_z, d_y,
                                                    count, d_ok, stream), "kzgx_verify_single_batch_device")
+
+    # ---- variable-base MSM over caller points, aggregated verification ----
+    def msm_points(self, points, scalars, inf=None):
+        """sum_k scalars[k] * points[k] over caller-supplied canonical affine points (no SRS needed)."""
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        n = pts.shape[0]
+        sc = as_scalars(scalars) if n else np.zeros((0, 4), dtype=np.uint64)
+        assert sc.shape[0] == n
+        f = None if inf is None else np.ascontiguousarray(inf, dtype=np.int32)
+        out = np.zeros(2 * self.w64, dtype=np.uint64)
+        oi = ctypes.c_int(0)
+        _chk(lib().kzgx_msm_g1_points(self.h, _p(pts) if n else None, None if f is None else f.ctypes.data_as(intp),
+                                      _p(sc) if n else None, n, _p(out), ctypes.byref(oi)), "kzgx_msm_g1_points")
+        return out, bool(oi.value)
+
+    def msm_points_device(self, d_points, d_inf, d_scalars, n, d_out, d_out_inf, stream=None):
+        """kzgx_msm_g1_points_device: device pointers (uint32 infinity flags or None), enqueued on stream."""
+        _chk(lib().kzgx_msm_g1_points_device(self.h, d_points, d_inf, d_scalars, n, d_out, d_out_inf, stream),
+             "kzgx_msm_g1_points_device")
+
+    def verify_aggregate(self, commits, proofs, zs, ys, challenges=None, commit_inf=None, proof_inf=None) -> bool:
+        """One pairing check of e(sum r_k proof_k, [tau]G2) == e(sum r_k (C_k - [y_k]G + [z_k] proof_k), G2);
+        challenges None = the library draws 128-bit values (r_0 = 1)."""
+        c = np.ascontiguousarray(commits, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        p = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        n = c.shape[0]
+        z = as_scalars(zs) if n else np.zeros((0, 4), dtype=np.uint64)
+        y = as_scalars(ys) if n else np.zeros((0, 4), dtype=np.uint64)
+        r = None if challenges is None else (as_scalars(challenges) if n else np.zeros((0, 4), dtype=np.uint64))
+        assert p.shape[0] == n and z.shape[0] == n and y.shape[0] == n and (r is None or r.shape[0] == n)
+        fc = None if commit_inf is None else np.ascontiguousarray(commit_inf, dtype=np.int32)
+        fp = None if proof_inf is None else np.ascontiguousarray(proof_inf, dtype=np.int32)
+        ok = ctypes.c_int(0)
+        _chk(lib().kzgx_verify_aggregate(self.h, _p(c) if n else None, None if fc is None else fc.ctypes.data_as(intp),
+                                         _p(p) if n else None, None if fp is None else fp.ctypes.data_as(intp),
+                                         _p(z) if n else None, _p(y) if n else None,
+                                         None if r is None or not n else _p(r), n, ctypes.byref(ok)),
+             "kzgx_verify_aggregate")
+        return bool(ok.value)
+
+    def verify_aggregate_device(self, d_commits, d_commit_inf, d_proofs, d_proof_inf, d_z, d_y, d_challenges, count,
+                                d_ok, stream=None):
+        """kzgx_verify_aggregate_device: device pointers, d_ok one uint32, enqueued on stream."""
+        _chk(lib().kzgx_verify_aggregate_device(self.h, d_commits, d_commit_inf, d_proofs, d_proof_inf, d_z, d_y,
+                                                d_challenges, count, d_ok, stream), "kzgx_verify_aggregate_device")

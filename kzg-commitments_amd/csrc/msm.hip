@@ -24,6 +24,7 @@
 // with any other correct evaluation of sum c_i [tau^i]G1.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <optional>
 
 #include "curve.hpp"
 #include "msm_merge.hpp"
@@ -145,7 +146,7 @@ KZGX_DEV void load_scalar(const uint32_t* p, uint32_t (&s)[8]) {
   s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
 }
 
-// Scalars are recoded per (MSM, count block) of SORT_BLK consecutive points.
+// Scalars are recoded per (bucket set, count block) of consecutive points.
 // Each count block keeps its own bucket histogram, so the sort needs no
 // global atomics: the scan turns the histograms into bucket offsets and
 // per-block write bases, and the scatter ranks entries with LDS atomics only.
@@ -155,44 +156,107 @@ KZGX_DEV void load_scalar(const uint32_t* p, uint32_t (&s)[8]) {
 constexpr uint32_t SORT_SPT = KZGX_SORT_SPT;  // scalars per thread in count / scatter
 constexpr uint32_t SORT_BLK = 256 * SORT_SPT;  // scalars per count block
 
-// pass 1: bucket histogram of every (MSM, count block), written in full
-template <int CB>
-__global__ __launch_bounds__(256) void k_msm_count(const uint32_t* __restrict__ scalars, uint32_t n, size_t stride_words,
-                                                   const uint8_t* __restrict__ inf, uint32_t* __restrict__ bcount,
-                                                   uint32_t nblk, uint32_t point_base, uint32_t point_stride) {
-  constexpr int W = Win<CB>::W;
-  constexpr uint32_t NB = Win<CB>::NB;
-  __shared__ uint32_t hist[NB];
-  const uint32_t b = blockIdx.y;
-  for (uint32_t k = threadIdx.x; k < NB; k += blockDim.x) hist[k] = 0;
-  __syncthreads();
-#pragma unroll 1
-  for (uint32_t j = 0; j < SORT_SPT; j++) {
-    const uint32_t i = blockIdx.x * SORT_BLK + j * 256 + threadIdx.x;
-    if (i < n && !inf[point_base + b * point_stride + i]) {
+// The three sort kernels serve every batched Pippenger.  What a bucket set
+// (blockIdx.y) sorts is its digit source, a small struct passed by value:
+//   SPT                  points per thread, so 256 SPT points per count block;
+//   digits_per_point(W)  entries a point can add to one bucket set (sizes the
+//                        scatter's LDS stage);
+//   entries_base(b)      the first entry word of bucket set b;
+//   digits<CB>(.., b, i, emit)   emit(d, row) for every non-zero signed digit
+//                        d of point i that belongs to bucket set b; row is
+//                        the digit's table row, the entry is row | sign << 31.
+// SrsSrc (msm_batch_impl): bucket set b is MSM b, every scalar adds all its W
+// digits, the rows are those of a window table over the SRS.  PointSrc
+// (msm_points_impl, with the variable-base section below) adds one digit.
+struct SrsSrc {
+  static constexpr uint32_t SPT = SORT_SPT;
+  static constexpr uint32_t digits_per_point(int W) { return (uint32_t)W; }
+  size_t stride_words;                // between the scalars of consecutive MSMs
+  uint32_t point_base, point_stride;  // scalar i of MSM b multiplies SRS point point_base + b point_stride + i
+  uint32_t n_rows;                    // points per window of the table
+  size_t emax;
+  KZGX_DEV size_t entries_base(uint32_t b) const { return b * emax; }
+  template <int CB, class F>
+  KZGX_DEV void digits(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf, uint32_t n, uint32_t b,
+                       uint32_t i, F emit) const {
+    const uint32_t ig = point_base + b * point_stride + i;  // SRS index of this scalar
+    if (i < n && !inf[ig]) {
       uint32_t s[8];
       load_scalar(scalars + b * stride_words + (size_t)i * 8, s);
       uint32_t carry = 0;
 #pragma unroll
-      for (int w = 0; w < W; w++) {
-        int d = digit_at<CB>(s, w, carry);
-        if (d != 0) atomicAdd(&hist[(d < 0 ? -d : d) - 1], 1u);
+      for (int w = 0; w < Win<CB>::W; w++) {
+        const int d = digit_at<CB>(s, w, carry);
+        if (d != 0) emit(d, (uint32_t)w * n_rows + ig);
       }
     }
   }
-  __syncthreads();
-  uint32_t* out = bcount + ((size_t)b * nblk + blockIdx.x) * NB;
-  for (uint32_t k = threadIdx.x; k < NB; k += blockDim.x) out[k] = hist[k];
+};
+
+KZGX_DEV uint32_t digit_bucket(int d) { return (uint32_t)((d < 0 ? -d : d) - 1); }
+
+// NB counters and the 256 threads of a block: dst[k] = src[k]
+template <uint32_t NB>
+KZGX_DEV void counters_copy(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src) {
+  for (uint32_t k = threadIdx.x; k < NB; k += 256) dst[k] = src[k];
 }
 
-// pass 2, one workgroup per MSM: bucket totals over the count blocks, an
+// Exclusive scan of NB LDS counters by the 256 threads of a block:
+// excl[k] = sum of cnt[k' < k] (excl may be cnt).  Thread t reads and writes
+// counters [t PER, t PER + PER) only, so it may have filled them itself just
+// before; it returns the sum through its last counter (thread 255: the
+// total).  part: 256 words of LDS.  No barrier after the last write.
+template <uint32_t NB>
+KZGX_DEV uint32_t counters_scan(const uint32_t* cnt, uint32_t* excl, uint32_t* part) {
+  constexpr uint32_t PER = NB / 256;  // NB is a multiple of 256 (c >= 9)
+  const uint32_t t = threadIdx.x;
+  uint32_t local = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < PER; j++) local += cnt[t * PER + j];
+  part[t] = local;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256; d <<= 1) {
+    uint32_t v = (t >= d) ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[t] - local;  // exclusive prefix of this thread's counters
+#pragma unroll
+  for (uint32_t j = 0; j < PER; j++) {
+    const uint32_t c = cnt[t * PER + j];
+    excl[t * PER + j] = run;
+    run += c;
+  }
+  return run;
+}
+
+// pass 1: bucket histogram of every (bucket set, count block), written in full
+template <int CB, class Src>
+__global__ __launch_bounds__(256) void k_msm_count(Src src, const uint32_t* __restrict__ scalars, uint32_t n,
+                                                   const uint8_t* __restrict__ inf, uint32_t* __restrict__ bcount,
+                                                   uint32_t nblk) {
+  constexpr uint32_t NB = Win<CB>::NB;
+  __shared__ uint32_t hist[NB];
+  const uint32_t b = blockIdx.y;
+  for (uint32_t k = threadIdx.x; k < NB; k += 256) hist[k] = 0;
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t j = 0; j < Src::SPT; j++) {
+    const uint32_t i = blockIdx.x * (256 * Src::SPT) + j * 256 + threadIdx.x;
+    src.template digits<CB>(scalars, inf, n, b, i, [&](int d, uint32_t) { atomicAdd(&hist[digit_bucket(d)], 1u); });
+  }
+  __syncthreads();
+  counters_copy<NB>(bcount + ((size_t)b * nblk + blockIdx.x) * NB, hist);
+}
+
+// pass 2, one workgroup per bucket set: bucket totals over the count blocks, an
 // exclusive scan -> offsets[b][0..NB], and the write base of every
 // (count block, bucket): bbase[b][blk][k] = offsets[k] + sum_{blk' < blk} count
 template <int CB>
 __global__ __launch_bounds__(256) void k_msm_scan(const uint32_t* __restrict__ bcount, uint32_t nblk,
                                                   uint32_t* __restrict__ offsets, uint32_t* __restrict__ bbase) {
   constexpr uint32_t NB = Win<CB>::NB;
-  constexpr uint32_t PER = NB / 256;  // NB is a multiple of 256 (c >= 9)
   __shared__ uint32_t tot[NB];
   __shared__ uint32_t part[256];
   const uint32_t b = blockIdx.x;
@@ -204,24 +268,7 @@ __global__ __launch_bounds__(256) void k_msm_scan(const uint32_t* __restrict__ b
     tot[k] = s;
   }
   __syncthreads();
-  uint32_t local = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < PER; j++) local += tot[t * PER + j];
-  part[t] = local;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1) {
-    uint32_t v = (t >= d) ? part[t - d] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = part[t] - local;  // exclusive prefix of this thread's buckets
-#pragma unroll
-  for (uint32_t j = 0; j < PER; j++) {
-    const uint32_t c = tot[t * PER + j];
-    tot[t * PER + j] = run;
-    run += c;
-  }
+  const uint32_t run = counters_scan<NB>(tot, tot, part);
   uint32_t* off = offsets + (size_t)b * (NB + 1);
   if (t == 255) off[NB] = run;
   __syncthreads();
@@ -241,86 +288,14 @@ __global__ __launch_bounds__(256) void k_msm_scan(const uint32_t* __restrict__ b
 // ranks from LDS atomics), then writes them out in that order: lanes of a
 // wavefront write consecutive positions of one bucket's run, so the stores
 // coalesce instead of landing as scattered 4-byte writes.  No global atomics.
-template <int CB>
-__global__ __launch_bounds__(256) void k_msm_scatter(const uint32_t* __restrict__ scalars, uint32_t n,
-                                                     size_t stride_words, const uint8_t* __restrict__ inf,
-                                                     const uint32_t* __restrict__ bcount,
-                                                     const uint32_t* __restrict__ bbase, uint32_t nblk,
-                                                     uint32_t* __restrict__ entries, size_t emax, uint32_t n_srs,
-                                                     uint32_t point_base, uint32_t point_stride) {
-  constexpr int W = Win<CB>::W;
-  constexpr uint32_t NB = Win<CB>::NB;
-  constexpr uint32_t PER = NB / 256;
-  __shared__ uint32_t stage[SORT_BLK * W];
-  __shared__ uint32_t lstart[NB + 1];
-  __shared__ uint32_t cur[NB];
-  __shared__ uint32_t part[256];
-  const uint32_t b = blockIdx.y;
-  const uint32_t t = threadIdx.x;
-  const size_t hb = ((size_t)b * nblk + blockIdx.x) * NB;
-  // local exclusive scan of this block's histogram
-  uint32_t local = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < PER; j++) {
-    const uint32_t c = bcount[hb + t * PER + j];
-    cur[t * PER + j] = c;
-    local += c;
-  }
-  part[t] = local;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1) {
-    uint32_t v = (t >= d) ? part[t - d] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = part[t] - local;
-#pragma unroll
-  for (uint32_t j = 0; j < PER; j++) {
-    const uint32_t c = cur[t * PER + j];
-    lstart[t * PER + j] = run;
-    cur[t * PER + j] = run;
-    run += c;
-  }
-  if (t == 255) lstart[NB] = run;
-  __syncthreads();
-  // rank every digit into the block's LDS stage
-#pragma unroll 1
-  for (uint32_t j = 0; j < SORT_SPT; j++) {
-    const uint32_t i = blockIdx.x * SORT_BLK + j * 256 + t;
-    const uint32_t ig = point_base + b * point_stride + i;  // SRS index of this scalar
-    if (i < n && !inf[ig]) {
-      uint32_t s[8];
-      load_scalar(scalars + b * stride_words + (size_t)i * 8, s);
-      uint32_t carry = 0;
-#pragma unroll
-      for (int w = 0; w < W; w++) {
-        int d = digit_at<CB>(s, w, carry);
-        if (d != 0) {
-          const uint32_t pos = atomicAdd(&cur[(d < 0 ? -d : d) - 1], 1u);
-#ifdef KZGX_SCATTER_DIRECT
-          const uint32_t kk = (uint32_t)((d < 0 ? -d : d) - 1);
-          entries[b * emax + bbase[hb + kk] + (pos - lstart[kk])] = ((uint32_t)w * n_srs + ig) | (d < 0 ? 0x80000000u : 0u);
-#else
-          stage[pos] = ((uint32_t)w * n_srs + ig) | (d < 0 ? 0x80000000u : 0u);
-#endif
-        }
-      }
-    }
-  }
-  __syncthreads();
-  for (uint32_t k = t; k < NB; k += 256) cur[k] = bbase[hb + k];  // global write bases
-  __syncthreads();
-#ifdef KZGX_SCATTER_DIRECT
-  (void)stage;
-#endif
-  uint32_t* out = entries + b * emax;
-#ifdef KZGX_SCATTER_DIRECT
-  const uint32_t total = 0;
-#else
+//
+// The write-out: the block's lstart[NB] staged entries, bucket k's at
+// stage[lstart[k] .. lstart[k + 1]), go to out[gbase[k] ..]
+template <uint32_t NB>
+KZGX_DEV void write_runs(const uint32_t* stage, const uint32_t* lstart, const uint32_t* gbase,
+                         uint32_t* __restrict__ out) {
   const uint32_t total = lstart[NB];
-#endif
-  for (uint32_t j = t; j < total; j += 256) {
+  for (uint32_t j = threadIdx.x; j < total; j += 256) {
     uint32_t lo = 0, hi = NB;  // bucket of position j: lstart[lo] <= j < lstart[hi]
     while (hi - lo > 1) {
       const uint32_t mid = (lo + hi) >> 1;
@@ -329,8 +304,47 @@ __global__ __launch_bounds__(256) void k_msm_scatter(const uint32_t* __restrict_
       else
         hi = mid;
     }
-    out[cur[lo] + (j - lstart[lo])] = stage[j];
+    out[gbase[lo] + (j - lstart[lo])] = stage[j];
   }
+}
+
+template <int CB, class Src>
+__global__ __launch_bounds__(256) void k_msm_scatter(Src src, const uint32_t* __restrict__ scalars, uint32_t n,
+                                                     const uint8_t* __restrict__ inf,
+                                                     const uint32_t* __restrict__ bcount,
+                                                     const uint32_t* __restrict__ bbase, uint32_t nblk,
+                                                     uint32_t* __restrict__ entries) {
+  constexpr uint32_t NB = Win<CB>::NB;
+  constexpr uint32_t PER = NB / 256;
+  __shared__ uint32_t stage[256 * Src::SPT * Src::digits_per_point(Win<CB>::W)];
+  __shared__ uint32_t lstart[NB + 1];
+  __shared__ uint32_t cur[NB];
+  __shared__ uint32_t part[256];
+  const uint32_t b = blockIdx.y;
+  const uint32_t t = threadIdx.x;
+  const size_t hb = ((size_t)b * nblk + blockIdx.x) * NB;
+  // local exclusive scan of this block's histogram: the buckets' starts in
+  // the stage, and the cursors the ranking advances from them
+#pragma unroll
+  for (uint32_t j = 0; j < PER; j++) cur[t * PER + j] = bcount[hb + t * PER + j];
+  const uint32_t run = counters_scan<NB>(cur, lstart, part);
+#pragma unroll
+  for (uint32_t j = 0; j < PER; j++) cur[t * PER + j] = lstart[t * PER + j];
+  if (t == 255) lstart[NB] = run;
+  __syncthreads();
+  // rank every digit into the block's LDS stage (pos < lstart[NB], the block's count of digits)
+#pragma unroll 1
+  for (uint32_t j = 0; j < Src::SPT; j++) {
+    const uint32_t i = blockIdx.x * (256 * Src::SPT) + j * 256 + t;
+    src.template digits<CB>(scalars, inf, n, b, i, [&](int d, uint32_t row) {
+      const uint32_t pos = atomicAdd(&cur[digit_bucket(d)], 1u);
+      stage[pos] = row | (d < 0 ? 0x80000000u : 0u);
+    });
+  }
+  __syncthreads();
+  counters_copy<NB>(cur, bbase + hb);  // global write bases
+  __syncthreads();
+  write_runs<NB>(stage, lstart, cur, entries + src.entries_base(b));
 }
 
 // pass 4: balanced bucket accumulation.  Thread s of an MSM owns the K
@@ -1344,6 +1358,68 @@ static int bucket_reduce(Ctx* ctx, MsmWs& ws, size_t batch, hipStream_t st, uint
   return KZGX_OK;
 }
 
+// entries per accumulation thread: the context's segment length, halved
+// (down to 8) while the grid would hold fewer than ~128k threads, so a
+// single or small batch of MSMs still spreads over the chip
+static uint32_t segment_len(const Ctx* ctx, size_t total_entries) {
+  uint32_t K = ctx->seg_k;
+  while (K > 8 && total_entries / K < 131072) K >>= 1;
+  return K;
+}
+
+// latency.hip: the segment merge with inlined additions (memory clauses off)
+int big_merge_inline(int curve, const uint32_t* heads, const uint32_t* tails, const uint32_t* tailk,
+                     const uint8_t* sstate, uint32_t smax, uint32_t nb, uint32_t nwg, uint32_t* bsum, uint32_t* ghead,
+                     uint32_t* gtail, uint32_t* gtailk, uint32_t* gflag, hipStream_t st);
+
+enum class Merge { Called, Inline };  // k_msm_merge | big_merge_inline (one bucket set)
+
+// Passes 4 and 4b of every Pippenger whose sort left `batch` bucket sets of up
+// to emax entries in ws.entries / ws.offsets: K entries per accumulation
+// thread from the rows of `table` (span accum_span), then the merge of the
+// bucket partials that cross segments and workgroups into ws.bsum.  The merge
+// opens the caller's span `reduce` (named reduce_span), which the caller
+// keeps open over its bucket reduction.
+// heads / tails / tailk / sstate: per-segment partials; gpart (ghead | gtail
+// points) and gmeta (gtailk | gflag): the workgroup-crossing ones.
+template <class C>
+static int accum_stage(Ctx* ctx, MsmWs& ws, size_t batch, size_t emax, uint32_t NB, const uint32_t* table, uint32_t K,
+                       hipStream_t st, Merge merge, const char* accum_span, const char* reduce_span,
+                       std::optional<ProfScope>& reduce) {
+  constexpr size_t XW = xyzz_words<C>(), XB = XW * sizeof(uint32_t);
+  const size_t smax = (emax + K - 1) / K;
+  const size_t nwg = (smax + ACC_WG - 1) / ACC_WG;
+  if (batch > 65535 || nwg > 65535) return KZGX_ERR_ARG;  // grid limits
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.bsum, batch * NB * XB, &ws.bsum_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.heads, batch * smax * XB, &ws.heads_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.tails, batch * smax * XB, &ws.tails_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.tailk, batch * smax * 4, &ws.tailk_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.sstate, batch * smax, &ws.sstate_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.gpart, batch * nwg * 2 * XB, &ws.gpart_b));
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.gmeta, batch * nwg * 2 * 4, &ws.gmeta_b));
+  uint32_t* ghead = ws.gpart;
+  uint32_t* gtail = ws.gpart + batch * nwg * XW;
+  uint32_t* gtailk = ws.gmeta;
+  uint32_t* gflag = ws.gmeta + batch * nwg;
+  {
+    ProfScope p(ctx, st, accum_span);
+    hipLaunchKernelGGL(k_msm_accum<C>, dim3((unsigned)((smax + 255) / 256), (unsigned)batch), dim3(256), 0, st,
+                       ws.entries, emax, ws.offsets, NB, table, K, (uint32_t)smax, ws.bsum, ws.heads, ws.tails,
+                       ws.tailk, ws.sstate);
+  }
+  reduce.emplace(ctx, st, reduce_span);
+  if (merge == Merge::Inline)
+    KZGX_TRY(big_merge_inline(ctx->curve, ws.heads, ws.tails, ws.tailk, ws.sstate, (uint32_t)smax, NB, (uint32_t)nwg,
+                              ws.bsum, ghead, gtail, gtailk, gflag, st));
+  else
+    hipLaunchKernelGGL(k_msm_merge<C>, dim3((unsigned)nwg, (unsigned)batch), dim3(ACC_WG), 0, st, ws.heads, ws.tails,
+                       ws.tailk, ws.sstate, (uint32_t)smax, NB, (uint32_t)nwg, ws.bsum, ghead, gtail, gtailk, gflag);
+  hipLaunchKernelGGL(k_msm_wg_fixup<C>, dim3((unsigned)((nwg + 63) / 64), (unsigned)batch), dim3(64), 0, st, NB,
+                     (uint32_t)nwg, ghead, gtail, gtailk, gflag, ws.bsum);
+  KZGX_TRY_HIP(hipGetLastError());
+  return KZGX_OK;
+}
+
 template <class C, int CB>
 int msm_batch_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, size_t batch, size_t stride_words, uint32_t* d_out,
                    uint32_t* d_out_inf, hipStream_t st, uint32_t point_base, uint32_t point_stride,
@@ -1351,45 +1427,27 @@ int msm_batch_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, size_t batch, 
   constexpr int W = Win<CB>::W;
   constexpr uint32_t NB = Win<CB>::NB;
   const size_t emax = (size_t)n * W;
-  // entries per accumulation thread: the context's segment length, halved
-  // (down to 8) while the grid would hold fewer than ~128k threads, so a
-  // single or small batch of MSMs still spreads over the chip
-  uint32_t K = ctx->seg_k;
-  while (K > 8 && batch * emax / K < 131072) K >>= 1;
-  const size_t smax = (emax + K - 1) / K;
-  const size_t nwg = (smax + ACC_WG - 1) / ACC_WG;
+  const uint32_t K = segment_len(ctx, batch * emax);
   const size_t nblk = (n + SORT_BLK - 1) / SORT_BLK;
   const size_t XB = xyzz_words<C>() * sizeof(uint32_t);
-  if (batch > 65535 || nblk > 65535 || nwg > 65535) return KZGX_ERR_ARG;  // grid limits
+  if (batch > 65535 || nblk > 65535) return KZGX_ERR_ARG;  // grid limits of the sort
   WsLease wsp = ctx->ws_for(st);
   if (!wsp) return KZGX_ERR_ARG;  // workspace binding failed (device sync error)
   MsmWs& ws = *wsp;
-  // counts: per-(MSM, count block) histograms; cursors: their write bases;
-  // heads / tails / tailk / flags: workgroup-crossing bucket partials
+  // counts: per-(MSM, count block) histograms; cursors: their write bases
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.counts, batch * nblk * NB * 4, &ws.counts_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.cursors, batch * nblk * NB * 4, &ws.cursors_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.offsets, batch * (NB + 1) * 4, &ws.offsets_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.entries, batch * emax * 4, &ws.entries_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.bsum, batch * NB * XB, &ws.bsum_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.heads, batch * smax * XB, &ws.heads_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.tails, batch * smax * XB, &ws.tails_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.tailk, batch * smax * 4, &ws.tailk_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.sstate, batch * smax, &ws.sstate_b));
-  // workgroup-crossing partials: ghead / gtail points, gtailk, gflag
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.gpart, batch * nwg * 2 * XB, &ws.gpart_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.gmeta, batch * nwg * 2 * 4, &ws.gmeta_b));
   const bool small = batch <= KZGX_SMALL_BATCH_J;
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.rt, batch * (NB / (small ? RED_J_SMALL : RED_J)) * 2 * XB, &ws.rt_b));
-  uint32_t* ghead = ws.gpart;
-  uint32_t* gtail = ws.gpart + batch * nwg * xyzz_words<C>();
-  uint32_t* gtailk = ws.gmeta;
-  uint32_t* gflag = ws.gmeta + batch * nwg;
+  const SrsSrc src{stride_words, point_base, point_stride, (uint32_t)n_rows, emax};
   dim3 blk(256);
   dim3 gs((unsigned)nblk, (unsigned)batch);
   {
     ProfScope p(ctx, st, "msm_count");
-    hipLaunchKernelGGL(k_msm_count<CB>, gs, blk, 0, st, d_scalars, (uint32_t)n, stride_words, ctx->d_inf, ws.counts,
-                       (uint32_t)nblk, point_base, point_stride);
+    hipLaunchKernelGGL((k_msm_count<CB, SrsSrc>), gs, blk, 0, st, src, d_scalars, (uint32_t)n, ctx->d_inf, ws.counts,
+                       (uint32_t)nblk);
   }
   {
     ProfScope p(ctx, st, "msm_scan");
@@ -1398,26 +1456,13 @@ int msm_batch_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, size_t batch, 
   }
   {
     ProfScope p(ctx, st, "msm_scatter");
-    hipLaunchKernelGGL(k_msm_scatter<CB>, gs, blk, 0, st, d_scalars, (uint32_t)n, stride_words, ctx->d_inf,
-                       ws.counts, ws.cursors, (uint32_t)nblk, ws.entries, emax, (uint32_t)n_rows, point_base, point_stride);
+    hipLaunchKernelGGL((k_msm_scatter<CB, SrsSrc>), gs, blk, 0, st, src, d_scalars, (uint32_t)n, ctx->d_inf, ws.counts,
+                       ws.cursors, (uint32_t)nblk, ws.entries);
   }
-  {
-    ProfScope p(ctx, st, "msm_accum");
-    hipLaunchKernelGGL(k_msm_accum<C>, dim3((unsigned)((smax + 255) / 256), (unsigned)batch), blk, 0, st, ws.entries,
-                       emax, ws.offsets, NB, d_tab, K, (uint32_t)smax, ws.bsum, ws.heads, ws.tails, ws.tailk,
-                       ws.sstate);
-  }
-  {
-    ProfScope p(ctx, st, "msm_reduce");
-    hipLaunchKernelGGL(k_msm_merge<C>, dim3((unsigned)nwg, (unsigned)batch), dim3(ACC_WG), 0, st, ws.heads, ws.tails,
-                       ws.tailk, ws.sstate, (uint32_t)smax, NB, (uint32_t)nwg, ws.bsum, ghead, gtail, gtailk, gflag);
-    hipLaunchKernelGGL(k_msm_wg_fixup<C>, dim3((unsigned)((nwg + 63) / 64), (unsigned)batch), dim3(64), 0, st, NB,
-                       (uint32_t)nwg, ghead, gtail, gtailk, gflag, ws.bsum);
-    if (small) return bucket_reduce<C, NB, RED_J_SMALL>(ctx, ws, batch, st, d_out, d_out_inf, xyzz_out);
-    return bucket_reduce<C, NB, RED_J>(ctx, ws, batch, st, d_out, d_out_inf, xyzz_out);
-  }
-  KZGX_TRY_HIP(hipGetLastError());
-  return KZGX_OK;
+  std::optional<ProfScope> reduce;
+  KZGX_TRY(accum_stage<C>(ctx, ws, batch, emax, NB, d_tab, K, st, Merge::Called, "msm_accum", "msm_reduce", reduce));
+  if (small) return bucket_reduce<C, NB, RED_J_SMALL>(ctx, ws, batch, st, d_out, d_out_inf, xyzz_out);
+  return bucket_reduce<C, NB, RED_J>(ctx, ws, batch, st, d_out, d_out_inf, xyzz_out);
 }
 
 // window 0 of the small table is the Montgomery SRS prefix (window 0 of the
@@ -1501,11 +1546,6 @@ static int msm_single_chunked(Ctx* ctx, const uint32_t* d_scalars, size_t n, uin
   return KZGX_OK;
 }
 
-// latency.hip: the segment merge with inlined additions (memory clauses off)
-int big_merge_inline(int curve, const uint32_t* heads, const uint32_t* tails, const uint32_t* tailk,
-                     const uint8_t* sstate, uint32_t smax, uint32_t nb, uint32_t nwg, uint32_t* bsum, uint32_t* ghead,
-                     uint32_t* gtail, uint32_t* gtailk, uint32_t* gflag, hipStream_t st);
-
 template <class C, int CB>
 static int msm_big_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t* d_out, uint32_t* d_out_inf,
                         hipStream_t st, uint32_t* xyzz_out) {
@@ -1517,8 +1557,7 @@ static int msm_big_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t*
   // measured 215 us for the 2^20 scatter); the scan reads nblk NB counters
   const uint32_t per = 2048;
   const size_t nblk = (n + per - 1) / per;
-  uint32_t K = ctx->seg_k;
-  while (K > 8 && emax / K < 131072) K >>= 1;
+  const uint32_t K = segment_len(ctx, emax);
   static const bool one_pass = std::getenv("KZGX_BIG_ONEPASS") != nullptr;  // A/B: the one-pass sort + merge
   if (!one_pass && (size_t)W * ctx->n_srs < ((size_t)1 << BigFine<CB>::IDX) && n <= (size_t)65535 * 1536) {
     const uint32_t per2 = big2_per<CB>();
@@ -1578,35 +1617,10 @@ static int msm_big_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t*
       return big_reduce_seg(ctx->curve, seg_off, ws.heads, NB, (uint32_t)s_ub, flag, ws.rt, d_out, d_out_inf, st,
                             xyzz_out);
     }
-    const size_t smax2 = (emax + K - 1) / K;
-    const size_t nwg2 = (smax2 + ACC_WG - 1) / ACC_WG;
-    if (nwg2 > 65535) return KZGX_ERR_ARG;
-    KZGX_TRY(dev_alloc(ctx, (void**)&ws.bsum, NB * XB, &ws.bsum_b));
-    KZGX_TRY(dev_alloc(ctx, (void**)&ws.heads, smax2 * XB, &ws.heads_b));
-    KZGX_TRY(dev_alloc(ctx, (void**)&ws.tails, smax2 * XB, &ws.tails_b));
-    KZGX_TRY(dev_alloc(ctx, (void**)&ws.tailk, smax2 * 4, &ws.tailk_b));
-    KZGX_TRY(dev_alloc(ctx, (void**)&ws.sstate, smax2, &ws.sstate_b));
-    KZGX_TRY(dev_alloc(ctx, (void**)&ws.gpart, nwg2 * 2 * XB, &ws.gpart_b));
-    KZGX_TRY(dev_alloc(ctx, (void**)&ws.gmeta, nwg2 * 2 * 4, &ws.gmeta_b));
-    {
-      ProfScope p(ctx, st, "msm_accum");
-      hipLaunchKernelGGL(k_msm_accum<C>, dim3((unsigned)((smax2 + 255) / 256), 1), dim3(256), 0, st, ws.entries, emax,
-                         ws.offsets, NB, ctx->d_table_big, K, (uint32_t)smax2, ws.bsum, ws.heads, ws.tails, ws.tailk,
-                         ws.sstate);
-    }
-    ProfScope p(ctx, st, "msm_reduce");
-    uint32_t* gh = ws.gpart;
-    uint32_t* gt = ws.gpart + nwg2 * xyzz_words<C>();
     static const bool merge_called = std::getenv("KZGX_BIG_MERGE_CALLED") != nullptr;  // A/B
-    if (merge_called)
-      hipLaunchKernelGGL(k_msm_merge<C>, dim3((unsigned)nwg2, 1), dim3(ACC_WG), 0, st, ws.heads, ws.tails, ws.tailk,
-                         ws.sstate, (uint32_t)smax2, NB, (uint32_t)nwg2, ws.bsum, gh, gt, ws.gmeta, ws.gmeta + nwg2);
-    else
-      KZGX_TRY(big_merge_inline(ctx->curve, ws.heads, ws.tails, ws.tailk, ws.sstate, (uint32_t)smax2, NB,
-                                (uint32_t)nwg2, ws.bsum, gh, gt, ws.gmeta, ws.gmeta + nwg2, st));
-    hipLaunchKernelGGL(k_msm_wg_fixup<C>, dim3((unsigned)((nwg2 + 63) / 64), 1), dim3(64), 0, st, NB, (uint32_t)nwg2,
-                       gh, gt, ws.gmeta, ws.gmeta + nwg2, ws.bsum);
-    KZGX_TRY_HIP(hipGetLastError());
+    std::optional<ProfScope> reduce;
+    KZGX_TRY(accum_stage<C>(ctx, ws, 1, emax, NB, ctx->d_table_big, K, st, merge_called ? Merge::Called : Merge::Inline,
+                            "msm_accum", "msm_reduce", reduce));
     return big_reduce(ctx->curve, ws.offsets, NB, ws.bsum, ws.rt, d_out, d_out_inf, st, xyzz_out);
   }
   // the one-pass sort's per-block LDS histograms hold NB counters: not at
@@ -1615,10 +1629,7 @@ static int msm_big_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t*
   if constexpr (CB > 16) {
     return KZGX_ERR_INTERNAL;
   } else {
-  const size_t smax = (emax + K - 1) / K;
-  const size_t nwg = (smax + ACC_WG - 1) / ACC_WG;
-  const size_t XB = xyzz_words<C>() * sizeof(uint32_t);
-  if (nblk > 65535 || nwg > 65535 || smax / 256 + 1 > 65535) return KZGX_ERR_ARG;
+  if (nblk > 65535) return KZGX_ERR_ARG;
   WsLease wsp = ctx->ws_for(st);
   if (!wsp) return KZGX_ERR_ARG;
   MsmWs& ws = *wsp;
@@ -1626,19 +1637,8 @@ static int msm_big_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t*
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.cursors, (nblk + 1) * NB * 4, &ws.cursors_b));  // bases | totals
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.offsets, (NB + 1) * 4, &ws.offsets_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.entries, emax * 4, &ws.entries_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.bsum, NB * XB, &ws.bsum_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.heads, smax * XB, &ws.heads_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.tails, smax * XB, &ws.tails_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.tailk, smax * 4, &ws.tailk_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.sstate, smax, &ws.sstate_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.gpart, nwg * 2 * XB, &ws.gpart_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.gmeta, nwg * 2 * 4, &ws.gmeta_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.rt, big_reduce_rt_bytes(ctx->curve, NB), &ws.rt_b));
   uint32_t* tot = ws.cursors + nblk * NB;
-  uint32_t* ghead = ws.gpart;
-  uint32_t* gtail = ws.gpart + nwg * xyzz_words<C>();
-  uint32_t* gtailk = ws.gmeta;
-  uint32_t* gflag = ws.gmeta + nwg;
   {
     ProfScope p(ctx, st, "msm_sort");
     hipLaunchKernelGGL(k_big_count<CB>, dim3((unsigned)nblk), dim3(BIG_TPB), 0, st, d_scalars, (uint32_t)n, ctx->d_inf,
@@ -1650,22 +1650,10 @@ static int msm_big_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t*
     hipLaunchKernelGGL(k_big_scatter<CB>, dim3((unsigned)nblk), dim3(BIG_TPB), 0, st, d_scalars, (uint32_t)n,
                        ctx->d_inf, per, ws.cursors, ws.entries, (uint32_t)ctx->n_srs);
   }
-  {
-    ProfScope p(ctx, st, "msm_accum");
-    hipLaunchKernelGGL(k_msm_accum<C>, dim3((unsigned)((smax + 255) / 256), 1), dim3(256), 0, st, ws.entries, emax,
-                       ws.offsets, NB, ctx->d_table_big, K, (uint32_t)smax, ws.bsum, ws.heads, ws.tails, ws.tailk,
-                       ws.sstate);
-  }
-  {
-    ProfScope p(ctx, st, "msm_reduce");
-    hipLaunchKernelGGL(k_msm_merge<C>, dim3((unsigned)nwg, 1), dim3(ACC_WG), 0, st, ws.heads, ws.tails, ws.tailk,
-                       ws.sstate, (uint32_t)smax, NB, (uint32_t)nwg, ws.bsum, ghead, gtail, gtailk, gflag);
-    hipLaunchKernelGGL(k_msm_wg_fixup<C>, dim3((unsigned)((nwg + 63) / 64), 1), dim3(64), 0, st, NB, (uint32_t)nwg,
-                       ghead, gtail, gtailk, gflag, ws.bsum);
-    KZGX_TRY_HIP(hipGetLastError());
-    KZGX_TRY(big_reduce(ctx->curve, ws.offsets, NB, ws.bsum, ws.rt, d_out, d_out_inf, st, xyzz_out));
-  }
-  return KZGX_OK;
+  std::optional<ProfScope> reduce;
+  KZGX_TRY(accum_stage<C>(ctx, ws, 1, emax, NB, ctx->d_table_big, K, st, Merge::Called, "msm_accum", "msm_reduce",
+                          reduce));
+  return big_reduce(ctx->curve, ws.offsets, NB, ws.bsum, ws.rt, d_out, d_out_inf, st, xyzz_out);
   }
 }
 
@@ -1692,9 +1680,11 @@ static int msm_big(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t* d_ou
 // Montgomery form once per call).  n is cut into chunks of VAR_CHUNK points
 // (the one-workgroup scan, as msm_single_chunked), so the batch is
 // chunks x W bucket sets of at most VAR_CHUNK entries each: set b = ch W + w
-// holds digit w of the scalars of chunk ch.  Count / scatter below emit one
-// digit per (point, window); accumulation, segment merge and the bucket
-// running sums are the batched Pippenger's kernels.  k_var_horner then sums
+// holds digit w of the scalars of chunk ch.  Every kernel of the batch is the
+// batched Pippenger's: the sort (k_msm_count / k_msm_scan / k_msm_scatter)
+// runs on PointSrc below, which emits one digit per (point, window), and
+// accumulation, segment merge and the bucket running sums see one more batch
+// of bucket sets over a table (accum_stage, bucket_reduce).  k_var_horner then sums
 // the chunks of every window and folds sum_w 2^(c w) S_w by Horner's rule
 // (c doublings a step, XYZZ, one affine conversion).  A window whose digits
 // are all zero (the upper half for 128-bit scalars) has no entries: its
@@ -1734,109 +1724,26 @@ KZGX_DEV int var_digit(const uint32_t (&s)[8], int w) {
   return mine;
 }
 
-// bucket histogram of every (bucket set, count block); layout as k_msm_count
-template <int CB>
-__global__ __launch_bounds__(256) void k_var_count(const uint32_t* __restrict__ scalars, uint32_t n, uint32_t L,
-                                                   const uint8_t* __restrict__ inf, uint32_t* __restrict__ bcount,
-                                                   uint32_t nblk) {
-  constexpr int W = Win<CB>::W;
-  constexpr uint32_t NB = Win<CB>::NB;
-  __shared__ uint32_t hist[NB];
-  const uint32_t b = blockIdx.y, ch = b / W;
-  const int w = (int)(b % W);
-  for (uint32_t k = threadIdx.x; k < NB; k += 256) hist[k] = 0;
-  __syncthreads();
-#pragma unroll 1
-  for (uint32_t j = 0; j < VAR_SPT; j++) {
-    const uint32_t li = blockIdx.x * VAR_BLK + j * 256 + threadIdx.x;
-    const uint32_t gi = ch * L + li;
+// the sort's digit source (see SrsSrc): bucket set b = ch W + w gets digit w
+// of point ch L + li, li < L; an entry is the point's row in ws.var_tab
+struct PointSrc {
+  static constexpr uint32_t SPT = VAR_SPT;
+  static constexpr uint32_t digits_per_point(int) { return 1; }
+  uint32_t L;  // points per chunk = entries per bucket set
+  KZGX_DEV size_t entries_base(uint32_t b) const { return (size_t)b * L; }
+  template <int CB, class F>
+  KZGX_DEV void digits(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf, uint32_t n, uint32_t b,
+                       uint32_t li, F emit) const {
+    constexpr int W = Win<CB>::W;
+    const uint32_t gi = b / W * L + li;
     if (li < L && gi < n && !inf[gi]) {
       uint32_t s[8];
       load_scalar(scalars + (size_t)gi * 8, s);
-      const int d = var_digit<CB>(s, w);
-      if (d != 0) atomicAdd(&hist[(d < 0 ? -d : d) - 1], 1u);
+      const int d = var_digit<CB>(s, (int)(b % W));
+      if (d != 0) emit(d, gi);
     }
   }
-  __syncthreads();
-  uint32_t* out = bcount + ((size_t)b * nblk + blockIdx.x) * NB;
-  for (uint32_t k = threadIdx.x; k < NB; k += 256) out[k] = hist[k];
-}
-
-// (point index | sign) entries of bucket set b into bucket order: the block
-// sorts its digits in LDS, then writes runs (as k_msm_scatter)
-template <int CB>
-__global__ __launch_bounds__(256) void k_var_scatter(const uint32_t* __restrict__ scalars, uint32_t n, uint32_t L,
-                                                     const uint8_t* __restrict__ inf,
-                                                     const uint32_t* __restrict__ bcount,
-                                                     const uint32_t* __restrict__ bbase, uint32_t nblk,
-                                                     uint32_t* __restrict__ entries) {
-  constexpr int W = Win<CB>::W;
-  constexpr uint32_t NB = Win<CB>::NB;
-  constexpr uint32_t PER = NB / 256;
-  __shared__ uint32_t stage[VAR_BLK];
-  __shared__ uint32_t lstart[NB + 1];
-  __shared__ uint32_t cur[NB];
-  __shared__ uint32_t part[256];
-  const uint32_t b = blockIdx.y, ch = b / W;
-  const int w = (int)(b % W);
-  const uint32_t t = threadIdx.x;
-  const size_t hb = ((size_t)b * nblk + blockIdx.x) * NB;
-  uint32_t local = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < PER; j++) {
-    const uint32_t c = bcount[hb + t * PER + j];
-    cur[t * PER + j] = c;
-    local += c;
-  }
-  part[t] = local;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1) {
-    uint32_t v = (t >= d) ? part[t - d] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = part[t] - local;
-#pragma unroll
-  for (uint32_t j = 0; j < PER; j++) {
-    const uint32_t c = cur[t * PER + j];
-    lstart[t * PER + j] = run;
-    cur[t * PER + j] = run;
-    run += c;
-  }
-  if (t == 255) lstart[NB] = run;
-  __syncthreads();
-#pragma unroll 1
-  for (uint32_t j = 0; j < VAR_SPT; j++) {
-    const uint32_t li = blockIdx.x * VAR_BLK + j * 256 + t;
-    const uint32_t gi = ch * L + li;
-    if (li < L && gi < n && !inf[gi]) {
-      uint32_t s[8];
-      load_scalar(scalars + (size_t)gi * 8, s);
-      const int d = var_digit<CB>(s, w);
-      if (d != 0) {
-        const uint32_t pos = atomicAdd(&cur[(d < 0 ? -d : d) - 1], 1u);  // < lstart[NB] <= VAR_BLK
-        stage[pos] = gi | (d < 0 ? 0x80000000u : 0u);
-      }
-    }
-  }
-  __syncthreads();
-  for (uint32_t k = t; k < NB; k += 256) cur[k] = bbase[hb + k];  // global write bases
-  __syncthreads();
-  uint32_t* out = entries + (size_t)b * L;
-  const uint32_t total = lstart[NB];
-  for (uint32_t j = t; j < total; j += 256) {
-    uint32_t lo = 0, hi = NB;  // bucket of position j: lstart[lo] <= j < lstart[hi]
-    while (hi - lo > 1) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (lstart[mid] <= j)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    out[cur[lo] + (j - lstart[lo])] = stage[j];
-  }
-}
+};
 
 // parts[ch W + w]: the XYZZ sum of window w of chunk ch.  Thread w sums its
 // window over the chunks; thread 0 then folds sum_w 2^(c w) S_w from the top
@@ -1901,52 +1808,29 @@ static int msm_points_impl(Ctx* ctx, MsmWs& ws, const uint32_t* d_scalars, size_
   constexpr uint32_t NB = Win<CB>::NB;
   const size_t batch = chunks * W;
   const size_t emax = L;  // one digit per (point, window)
-  uint32_t K = ctx->seg_k;
-  while (K > 8 && batch * emax / K < 131072) K >>= 1;
-  const size_t smax = (emax + K - 1) / K;
-  const size_t nwg = (smax + ACC_WG - 1) / ACC_WG;
+  const uint32_t K = segment_len(ctx, batch * emax);
   const size_t nblk = (L + VAR_BLK - 1) / VAR_BLK;
   const size_t XB = xyzz_words<C>() * sizeof(uint32_t);
-  if (batch > 65535 || nblk > 65535 || nwg > 65535) return KZGX_ERR_ARG;  // grid limits
+  if (batch > 65535 || nblk > 65535) return KZGX_ERR_ARG;  // grid limits of the sort
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.counts, batch * nblk * NB * 4, &ws.counts_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.cursors, batch * nblk * NB * 4, &ws.cursors_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.offsets, batch * (NB + 1) * 4, &ws.offsets_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.entries, batch * emax * 4, &ws.entries_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.bsum, batch * NB * XB, &ws.bsum_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.heads, batch * smax * XB, &ws.heads_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.tails, batch * smax * XB, &ws.tails_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.tailk, batch * smax * 4, &ws.tailk_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.sstate, batch * smax, &ws.sstate_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.gpart, batch * nwg * 2 * XB, &ws.gpart_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.gmeta, batch * nwg * 2 * 4, &ws.gmeta_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.rt, batch * (NB / RED_J) * 2 * XB, &ws.rt_b));
-  uint32_t* ghead = ws.gpart;
-  uint32_t* gtail = ws.gpart + batch * nwg * xyzz_words<C>();
-  uint32_t* gtailk = ws.gmeta;
-  uint32_t* gflag = ws.gmeta + batch * nwg;
+  const PointSrc src{(uint32_t)L};
   dim3 blk(256);
   dim3 gs((unsigned)nblk, (unsigned)batch);
   {
     ProfScope p(ctx, st, "var_sort");
-    hipLaunchKernelGGL(k_var_count<CB>, gs, blk, 0, st, d_scalars, (uint32_t)n, (uint32_t)L, ws.var_inf, ws.counts,
+    hipLaunchKernelGGL((k_msm_count<CB, PointSrc>), gs, blk, 0, st, src, d_scalars, (uint32_t)n, ws.var_inf, ws.counts,
                        (uint32_t)nblk);
     hipLaunchKernelGGL(k_msm_scan<CB>, dim3((unsigned)batch), blk, 0, st, ws.counts, (uint32_t)nblk, ws.offsets,
                        ws.cursors);
-    hipLaunchKernelGGL(k_var_scatter<CB>, gs, blk, 0, st, d_scalars, (uint32_t)n, (uint32_t)L, ws.var_inf, ws.counts,
-                       ws.cursors, (uint32_t)nblk, ws.entries);
+    hipLaunchKernelGGL((k_msm_scatter<CB, PointSrc>), gs, blk, 0, st, src, d_scalars, (uint32_t)n, ws.var_inf,
+                       ws.counts, ws.cursors, (uint32_t)nblk, ws.entries);
   }
-  {
-    ProfScope p(ctx, st, "var_accum");
-    hipLaunchKernelGGL(k_msm_accum<C>, dim3((unsigned)((smax + 255) / 256), (unsigned)batch), blk, 0, st, ws.entries,
-                       emax, ws.offsets, NB, ws.var_tab, K, (uint32_t)smax, ws.bsum, ws.heads, ws.tails, ws.tailk,
-                       ws.sstate);
-  }
-  ProfScope p(ctx, st, "var_reduce");
-  hipLaunchKernelGGL(k_msm_merge<C>, dim3((unsigned)nwg, (unsigned)batch), dim3(ACC_WG), 0, st, ws.heads, ws.tails,
-                     ws.tailk, ws.sstate, (uint32_t)smax, NB, (uint32_t)nwg, ws.bsum, ghead, gtail, gtailk, gflag);
-  hipLaunchKernelGGL(k_msm_wg_fixup<C>, dim3((unsigned)((nwg + 63) / 64), (unsigned)batch), dim3(64), 0, st, NB,
-                     (uint32_t)nwg, ghead, gtail, gtailk, gflag, ws.bsum);
-  KZGX_TRY_HIP(hipGetLastError());
+  std::optional<ProfScope> reduce;
+  KZGX_TRY(accum_stage<C>(ctx, ws, batch, emax, NB, ws.var_tab, K, st, Merge::Called, "var_accum", "var_reduce", reduce));
   return bucket_reduce<C, NB, RED_J>(ctx, ws, batch, st, nullptr, nullptr, ws.var_parts);
 }
 

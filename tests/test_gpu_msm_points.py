@@ -149,6 +149,27 @@ def test_count_block_boundaries(name, C, n, ctxs, powers):
     check(ctx, name, C, P[:n], K.random_scalars(C, n, seed=1000 + n), d[:n])
 
 
+def tiled_msm_matches_one_scalar_mul(ctx, name, C, P, d, n):
+    """64 distinct points repeat, so the expected point is one scalar multiplication:
+    [sum s_k d_(k mod 64)]G"""
+    sc = K.random_scalars(C, n, seed=n)
+    pts = np.tile(P[:64], ((n + 63) // 64, 1))[:n]
+    out, oi = ctx.msm_points(pts, scalars(sc))
+    sums = [sum(sc[j::64]) for j in range(64)]
+    e = sum(s * dk for s, dk in zip(sums, d[:64])) % C.r
+    assert got_point(name, out, oi) == corc.scalar_mul(name, (C.gx, C.gy), e)
+
+
+@pytest.mark.parametrize("name,C", CURVES)
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 8193])
+def test_point_count_block_boundaries(name, C, n, ctxs, powers):
+    """the point path's count block is 4096 points (the 512 above is the SRS path's): one block
+    short by a point, full, one point over, and two full blocks and a point"""
+    ctx = ctxs(name)
+    P, d = powers(name, C)
+    tiled_msm_matches_one_scalar_mul(ctx, name, C, P, d, n)
+
+
 @pytest.mark.parametrize("name,C", CURVES)
 def test_one_bucket_spans_many_segments(name, C, ctxs, powers):
     """1000 copies of one (point, scalar) pair among 500 random terms: each window's bucket of that
@@ -173,16 +194,10 @@ def test_one_bucket_spans_many_segments(name, C, ctxs, powers):
 @pytest.mark.parametrize("name,C", CURVES)
 @pytest.mark.parametrize("n", [20001, 40001, (1 << 17) + 4097])
 def test_wider_windows_and_chunks(name, C, n, ctxs, powers):
-    """the 11-, 12- and 13-bit windows, and two chunks (2^17 points and an odd rest).  64 distinct
-    points repeat, so the expected point is one scalar multiplication: [sum s_k d_(k mod 64)]G"""
+    """the 11-, 12- and 13-bit windows, and two chunks (2^17 points and an odd rest)"""
     ctx = ctxs(name)
     P, d = powers(name, C)
-    sc = K.random_scalars(C, n, seed=n)
-    pts = np.tile(P[:64], ((n + 63) // 64, 1))[:n]
-    out, oi = ctx.msm_points(pts, scalars(sc))
-    sums = [sum(sc[j::64]) for j in range(64)]
-    e = sum(s * dk for s, dk in zip(sums, d[:64])) % C.r
-    assert got_point(name, out, oi) == corc.scalar_mul(name, (C.gx, C.gy), e)
+    tiled_msm_matches_one_scalar_mul(ctx, name, C, P, d, n)
 
 
 @pytest.mark.parametrize("name,C", CURVES)

@@ -211,6 +211,10 @@ KZGX_DEV void lat_store_affine(const Xyzz<C>& acc, uint32_t b, uint32_t lane, ui
 // last of the NG group folders folds those (two fold levels of <= 64
 // partials each instead of one wavefront summing Q / 64 partials per lane).
 // cnt[b (NG + 1)]: the final arrival counter, then one per group.
+// coop: the folds' last levels as cooperative additions; the host always
+// passes 1.  It stays a run-time argument (and xyzz_wave_sum / lat_fold keep
+// their shuffle-only arm) because the kernels compiled without it measured
+// 2-4 us slower per single commit / proof (profiles/ab_switch_retire.json).
 template <class C, int CB>
 __global__ __launch_bounds__(64) void k_fixed_accum_lat(const uint32_t* __restrict__ scalars, uint32_t n,
                                                         uint32_t n_pad, size_t stride_words,
@@ -344,11 +348,14 @@ KZGX_DEV void lat_store_affine(const Xyzz<C>& acc, uint32_t b, uint32_t lane, ui
 // A thread that starts inside point i runs the digit recoding of i's lower
 // windows for their carry only.  The lookup of the next term is in flight
 // during the addition of the current one.  lane_parts: every thread stores
-// its partial (part[b][t], for k_fixed_fold3); else the wavefront folds its
-// 64 partials with 6 shuffle additions before one lane stores (round 5: the
-// first 64:1 level of the reduction without a launch -- but 6 full additions
-// on every one of the ~3 resident waves per SIMD, ~90 us of a 131 073-point
-// shard's 0.4 ms accumulation).
+// its partial (part[b][t], for the fold launches); else the wavefront folds
+// its 64 partials with 6 shuffle additions before one lane stores (round 5:
+// the first 64:1 level of the reduction without a launch -- but 6 full
+// additions on every one of the ~3 resident waves per SIMD, ~90 us of a
+// 131 073-point shard's 0.4 ms accumulation).  The host always passes
+// lane_parts = 1; the parameter and the other arm stay because hipcc (ROCm
+// 7.2) spills 16 VGPRs instead of 7 (BLS12-381: 28 instead of 9) in the
+// kernel without them (profiles/ab_switch_retire.json).
 // --------------------------------------------------------------------------
 template <class C, int CB>
 __global__ __launch_bounds__(64, fixed_accum_waves<C>()) void k_fixed_accum_flat(
@@ -436,9 +443,9 @@ __global__ __launch_bounds__(64, fixed_accum_waves<C>()) void k_fixed_accum_flat
   if (threadIdx.x == 0) xyzz_store<C>(part + ((size_t)b * (T / 64) + t / 64) * XW, acc);
 }
 
-// One fold level as its own launch (the default; KZGX_FOLD3_SPLIT=0 runs
-// k_fixed_fold3's arrival counters and device-scope fences): wavefront g
-// folds in[g per, g per + per) into out[g]; with fin, group g = MSM b's last
+// One fold level as its own launch (taken when the first level's P1 wavefronts
+// form whole groups of 64; k_fixed_fold3 otherwise): wavefront g folds
+// in[g per, g per + per) into out[g]; with fin, group g = MSM b's last
 // level, stored as the XYZZ record or converted to affine
 template <class C>
 __global__ __launch_bounds__(64) void k_fold_level(const uint32_t* __restrict__ in, uint32_t per,
@@ -533,25 +540,22 @@ int fixed_msm_win(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n,
                   uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st, uint32_t* xyzz_out) {
   const size_t XB = xyzz_words<C>() * sizeof(uint32_t);
   // latency path: a few MSMs of <= 2^14 points (k_fixed_accum_lat)
-  static const bool lat_off = std::getenv("KZGX_NO_FIXED_LAT") != nullptr;
   const size_t n_pad = (n + 63) / 64 * 64;
-  if (batch <= 16 && !xyzz_out && n_pad <= 16384 && ft.pts_per_thread == 0 && !lat_off) {
+  if (batch <= 16 && !xyzz_out && n_pad <= 16384 && ft.pts_per_thread == 0) {
     constexpr int W = FixedWin<C, CB>::W;
-    // G window groups of WG windows over up to 2^14 threads per MSM
-    // (KZGX_LAT_THREADS: the single-MSM count, A/B; 2^16 measured slower:
-    // degree 4096 0.233 vs 0.202 ms, profiles/r04_lat_ab_coop_threads.txt):
-    // degree 4096 takes 3 groups of 8 windows (195 wavefront partials,
-    // folded in two levels), degree 128 one window per thread
-    static const size_t lat_threads = std::getenv("KZGX_LAT_THREADS") ? std::strtoul(std::getenv("KZGX_LAT_THREADS"), nullptr, 10) : 16384;
-    const size_t per_msm = std::max<size_t>(std::min<size_t>(lat_threads, 16384), lat_threads / batch);
-    int G = (int)std::min<size_t>(W, std::max<size_t>(1, per_msm / n_pad));
+    // G window groups of WG windows over up to 2^14 threads per MSM (2^16
+    // measured slower: degree 4096 0.233 vs 0.202 ms,
+    // profiles/r04_lat_ab_coop_threads.txt): degree 4096 takes 3 groups of 8
+    // windows (195 wavefront partials, folded in two levels), degree 128 one
+    // window per thread
+    constexpr size_t kLatThreads = 16384;
+    int G = (int)std::min<size_t>(W, std::max<size_t>(1, kLatThreads / n_pad));
     int WG = (W + G - 1) / G;
     // between 64 and 128 partials, one more window per thread when that
     // leaves <= 64 partials (a fold with no strided level: a mixed addition
     // instead of an XYZZ one on the chain; degree 128 / 256 commits -2.5 us,
-    // profiles/r04_lat_ab_q64_qwg8.txt; KZGX_LAT_Q64=0 turns it off, A/B)
-    static const bool q64 = !(std::getenv("KZGX_LAT_Q64") && std::getenv("KZGX_LAT_Q64")[0] == '0');
-    if (q64 && n_pad * G / 64 > 64 && n_pad * G / 64 <= 128) {
+    // profiles/r04_lat_ab_q64_qwg8.txt)
+    if (n_pad * G / 64 > 64 && n_pad * G / 64 <= 128) {
       const int G2 = (int)(64 * 64 / n_pad);
       if (G2 >= 1 && (W + G2 - 1) / G2 <= WG + 1) WG = (W + G2 - 1) / G2;
     }
@@ -567,12 +571,10 @@ int fixed_msm_win(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n,
       KZGX_TRY_HIP(hipMemsetAsync(wsp->lat_cnt, 0, kCnt * sizeof(uint32_t), st));
     }
     if (NG > 16 || batch * (NG + 1) > kCnt) return KZGX_ERR_ARG;  // unreachable: Q <= 2^16 / 64
-    // KZGX_NO_LAT_COOP: the last fold levels as plain shuffle additions (A/B)
-    static const bool coop_off = std::getenv("KZGX_NO_LAT_COOP") != nullptr;
     ProfScope p(ctx, st, "msm_accum");
     hipLaunchKernelGGL((k_fixed_accum_lat<C, CB>), dim3(Q, (unsigned)batch), dim3(64), 0, st, d_scalars, (uint32_t)n,
                        (uint32_t)n_pad, stride_words, ft.d, tab_strides<C>(ft), fixed_inf(ft), WG, Q, wsp->fpart,
-                       wsp->lat_cnt, d_out, d_out_inf, coop_off ? 0 : 1, NG, wsp->fpart + batch * Q * XB / 4);
+                       wsp->lat_cnt, d_out, d_out_inf, 1, NG, wsp->fpart + batch * Q * XB / 4);
     KZGX_TRY_HIP(hipGetLastError());
     return KZGX_OK;
   }
@@ -591,73 +593,49 @@ int fixed_msm_win(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n,
     constexpr int W = FixedWin<C, CB>::W;
     const size_t terms = n * (size_t)W;
     if (batch <= 16 && ft.pts_per_thread == 0 && !flat_off && terms * batch >= 8 * kSlots) {
-      // KZGX_FLAT_TMULT: threads per resident-lane slot (A/B)
-      static const size_t tmult = std::getenv("KZGX_FLAT_TMULT") ? std::strtoul(std::getenv("KZGX_FLAT_TMULT"), nullptr, 10) : 1;
-      const uint32_t T = (uint32_t)std::max<size_t>(4096, kSlots * (tmult ? tmult : 1) / batch / 4096 * 4096);
+      const uint32_t T = (uint32_t)std::max<size_t>(4096, kSlots / batch / 4096 * 4096);  // one thread per slot
       const uint32_t Q = (uint32_t)((terms + T - 1) / T);
       WsLease wsp = ctx->ws_for(st);
       if (!wsp) return KZGX_ERR_ARG;
       MsmWs& ws = *wsp;
-      // round 6: per-lane partials and the one-launch three-level fold
-      // (k_fixed_fold3); KZGX_FLAT_WAVEFOLD=1 keeps round 5's in-wave fold
-      // and reduce launches (A/B)
-      static const bool wavefold = std::getenv("KZGX_FLAT_WAVEFOLD") && std::getenv("KZGX_FLAT_WAVEFOLD")[0] == '1';
+      // per-lane partials, folded in three levels of kPer, 64 and NG
+      constexpr uint32_t kPer = 256;    // partials per first-level wavefront
       constexpr size_t kCnt = 16 * 17;  // the lat path's counter block
-      // per: partials per first-level wavefront (KZGX_FOLD3_PER, A/B: 64 / 128 / 256)
-      static const uint32_t per = std::getenv("KZGX_FOLD3_PER") ? (uint32_t)std::strtoul(std::getenv("KZGX_FOLD3_PER"), nullptr, 10) : 256u;
-      const uint32_t P1 = T / per, NG = (P1 + 63) / 64;  // T is a multiple of 4096
-      if (!wavefold && (per == 64 || per == 128 || per == 256 || per == 512) && batch * (NG + 1) <= kCnt) {
-        KZGX_TRY(dev_alloc(ctx, (void**)&ws.fpart, batch * (size_t)T * XB, &ws.fpart_b));
-        KZGX_TRY(dev_alloc(ctx, (void**)&ws.fsum, batch * (size_t)(P1 + NG) * XB, &ws.fsum_b));
-        if (!ws.lat_cnt) {  // arrival counters, zero between calls
-          KZGX_TRY_HIP(hipMalloc((void**)&ws.lat_cnt, kCnt * sizeof(uint32_t)));
-          KZGX_TRY_HIP(hipMemsetAsync(ws.lat_cnt, 0, kCnt * sizeof(uint32_t), st));
-        }
-        {
-          ProfScope p(ctx, st, "msm_accum");
-          hipLaunchKernelGGL((k_fixed_accum_flat<C, CB>), dim3(T / 64, (unsigned)batch), dim3(64), 0, st, d_scalars,
-                             (uint32_t)n, stride_words, ft.d, tab_strides<C>(ft), fixed_inf(ft), Q, T, ws.fpart, 1u);
-        }
-        ProfScope p(ctx, st, "msm_reduce");
-        // three launches by default: measured 15-20 us faster than
-        // k_fixed_fold3's one launch on the same box (131 073 points, c = 10:
-        // 0.438-0.458 vs 0.461-0.480 ms, profiles/r06_shard_fixed.jsonl) --
-        // the arrival pattern's device-scope release fences write back the
-        // L2 that still holds the accumulation's 28 MB of partials, where a
-        // kernel boundary does it once.  KZGX_FOLD3_SPLIT=0: k_fixed_fold3 (A/B)
-        static const bool split = !(std::getenv("KZGX_FOLD3_SPLIT") && std::getenv("KZGX_FOLD3_SPLIT")[0] == '0');
-        if (split && per == 256 && P1 % 64 == 0) {
-          uint32_t* f1 = ws.fsum;
-          uint32_t* f2 = ws.fsum + batch * (size_t)P1 * xyzz_words<C>();
-          hipLaunchKernelGGL(k_fold_level<C>, dim3(batch * P1), dim3(64), 0, st, ws.fpart, 256u, f1, 0, nullptr,
-                             nullptr, nullptr);
-          hipLaunchKernelGGL(k_fold_level<C>, dim3(batch * NG), dim3(64), 0, st, f1, 64u, f2, 0, nullptr, nullptr,
-                             nullptr);
-          hipLaunchKernelGGL(k_fold_level<C>, dim3(batch), dim3(64), 0, st, f2, NG, nullptr, 1, d_out, d_out_inf,
-                             xyzz_out);
-          KZGX_TRY_HIP(hipGetLastError());
-          return KZGX_OK;
-        }
-        hipLaunchKernelGGL(k_fixed_fold3<C>, dim3(P1, (unsigned)batch), dim3(64), 0, st, ws.fpart, per, P1, NG,
-                           ws.fsum, ws.fsum + batch * (size_t)P1 * xyzz_words<C>(), ws.lat_cnt, d_out, d_out_inf,
+      const uint32_t P1 = T / kPer, NG = (P1 + 63) / 64;  // T is a multiple of 4096 and <= kSlots: NG <= 12
+      static_assert(16 * (kSlots / 4096 * 4096 / kPer / 64 + 1) <= kCnt, "k_fixed_fold3's counters: batch (NG + 1)");
+      KZGX_TRY(dev_alloc(ctx, (void**)&ws.fpart, batch * (size_t)T * XB, &ws.fpart_b));
+      KZGX_TRY(dev_alloc(ctx, (void**)&ws.fsum, batch * (size_t)(P1 + NG) * XB, &ws.fsum_b));
+      if (!ws.lat_cnt) {  // arrival counters, zero between calls
+        KZGX_TRY_HIP(hipMalloc((void**)&ws.lat_cnt, kCnt * sizeof(uint32_t)));
+        KZGX_TRY_HIP(hipMemsetAsync(ws.lat_cnt, 0, kCnt * sizeof(uint32_t), st));
+      }
+      {
+        ProfScope p(ctx, st, "msm_accum");
+        hipLaunchKernelGGL((k_fixed_accum_flat<C, CB>), dim3(T / 64, (unsigned)batch), dim3(64), 0, st, d_scalars,
+                           (uint32_t)n, stride_words, ft.d, tab_strides<C>(ft), fixed_inf(ft), Q, T, ws.fpart, 1u);
+      }
+      ProfScope p(ctx, st, "msm_reduce");
+      // three launches where the levels divide evenly: measured 15-20 us
+      // faster than k_fixed_fold3's one launch on the same box (131 073
+      // points, c = 10: 0.438-0.458 vs 0.461-0.480 ms,
+      // profiles/r06_shard_fixed.jsonl) -- the arrival pattern's device-scope
+      // release fences write back the L2 that still holds the accumulation's
+      // 28 MB of partials, where a kernel boundary does it once
+      if (P1 % 64 == 0) {
+        uint32_t* f1 = ws.fsum;
+        uint32_t* f2 = ws.fsum + batch * (size_t)P1 * xyzz_words<C>();
+        hipLaunchKernelGGL(k_fold_level<C>, dim3(batch * P1), dim3(64), 0, st, ws.fpart, kPer, f1, 0, nullptr,
+                           nullptr, nullptr);
+        hipLaunchKernelGGL(k_fold_level<C>, dim3(batch * NG), dim3(64), 0, st, f1, 64u, f2, 0, nullptr, nullptr,
+                           nullptr);
+        hipLaunchKernelGGL(k_fold_level<C>, dim3(batch), dim3(64), 0, st, f2, NG, nullptr, 1, d_out, d_out_inf,
                            xyzz_out);
         KZGX_TRY_HIP(hipGetLastError());
         return KZGX_OK;
       }
-      KZGX_TRY(dev_alloc(ctx, (void**)&ws.fpart, batch * (T / 64) * XB, &ws.fpart_b));
-      KZGX_TRY(dev_alloc(ctx, (void**)&ws.fsum, batch * (T / 4096) * XB, &ws.fsum_b));
-      {
-        ProfScope p(ctx, st, "msm_accum");
-        hipLaunchKernelGGL((k_fixed_accum_flat<C, CB>), dim3(T / 64, (unsigned)batch), dim3(64), 0, st, d_scalars,
-                           (uint32_t)n, stride_words, ft.d, tab_strides<C>(ft), fixed_inf(ft), Q, T, ws.fpart, 0u);
-      }
-      ProfScope p(ctx, st, "msm_reduce");
-      // T / 64 wavefront partials per MSM: one more 64:1 level, then one
-      // wavefront per MSM over the T / 4096 left, then a thread per MSM
-      const size_t g2 = batch * (T / 4096);
-      fixed_reduce_launch<C>(ws.fpart, 64u, (uint32_t)g2, ws.fsum, st);
-      fixed_reduce_launch<C>(ws.fsum, T / 4096, (uint32_t)batch, ws.fpart, st);
-      fixed_finish_launch<C>(ws.fpart, (uint32_t)batch, d_out, d_out_inf, xyzz_out, st);
+      hipLaunchKernelGGL(k_fixed_fold3<C>, dim3(P1, (unsigned)batch), dim3(64), 0, st, ws.fpart, kPer, P1, NG,
+                         ws.fsum, ws.fsum + batch * (size_t)P1 * xyzz_words<C>(), ws.lat_cnt, d_out, d_out_inf,
+                         xyzz_out);
       KZGX_TRY_HIP(hipGetLastError());
       return KZGX_OK;
     }
@@ -666,12 +644,9 @@ int fixed_msm_win(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n,
   // automatic: 16 points per thread from 64 MSMs; BLS12-381 from 2048 MSMs
   // 65 (one residency at two waves per SIMD, the cfg4 shape: +2.4% on the
   // default table's batches, profiles/r04_ab_ppt_auto.json; BN254 22 vs 16
-  // measured +0.3%, kept); else enough threads to fill the chip.
-  // KZGX_PPT_AUTO_BIG: the count from 1024 MSMs (A/B)
-  static const uint32_t ppt_env = std::getenv("KZGX_PPT_AUTO_BIG") ? (uint32_t)std::strtoul(std::getenv("KZGX_PPT_AUTO_BIG"), nullptr, 10) : 0u;
+  // measured +0.3%, kept); else enough threads to fill the chip
   if (P0 == 0) {
-    if (ppt_env && batch >= 1024) P0 = ppt_env;
-    else if (C::Fp29::L > 9 && batch >= 2048) P0 = 65;
+    if (C::Fp29::L > 9 && batch >= 2048) P0 = 65;
     else P0 = batch >= 64 ? 16u : (uint32_t)std::max<size_t>(1, (n * batch + kSlots - 1) / kSlots);
   }
   uint32_t T = (uint32_t)(64 * ((n + 64 * (size_t)P0 - 1) / (64 * (size_t)P0)));

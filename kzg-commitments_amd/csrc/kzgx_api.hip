@@ -92,7 +92,7 @@ size_t g_cache_bytes[64];
 std::map<void*, size_t> g_block_bytes;  // true size of each block table_malloc handed out
 int g_live_ctx[64];  // live contexts per device (guarded by g_table_mu)
 bool table_cache_off() {
-  static const bool off = std::getenv("KZGX_NO_TABLE_CACHE") && std::getenv("KZGX_NO_TABLE_CACHE")[0] == '1';
+  static const bool off = kzgx::env_is_1("KZGX_NO_TABLE_CACHE");
   return off;
 }
 int current_device() {
@@ -1285,10 +1285,11 @@ int side_ready(kzgx_ctx* ctx) {
   return KZGX_OK;
 }
 
-// KZGX_PAIR2_SPLIT=1: the multi-point verify's pairing as round 6's two
-// launches (k_vlines_wave, then k_pair2_wave) instead of k_pair2_fused (A/B)
+// KZGX_PAIR2_SPLIT=1 (tests/test_gpu_env_hooks.py): the multi-point verify's
+// pairing as two launches (k_vlines_wave, then k_pair2_wave) from the start,
+// the path k_pair2_fused otherwise falls back to when it reports ok == 2
 bool split_pair2() {
-  static const bool on = std::getenv("KZGX_PAIR2_SPLIT") && std::getenv("KZGX_PAIR2_SPLIT")[0] == '1';
+  static const bool on = kzgx::env_is_1("KZGX_PAIR2_SPLIT");
   return on;
 }
 
@@ -1726,7 +1727,7 @@ namespace {
 // build (the reference's benchmark times each first call,
 // benchmark/benchmark.cpp:40-66).  KZGX_LAZY_SETUP=1 leaves them to first use.
 int setup_finish(kzgx_ctx* ctx) {
-  static const bool lazy = std::getenv("KZGX_LAZY_SETUP") && std::getenv("KZGX_LAZY_SETUP")[0] == '1';
+  static const bool lazy = kzgx::env_is_1("KZGX_LAZY_SETUP");
   if (lazy || ctx->c.n_srs == 0 || ctx->n_srs2 < 2) return KZGX_OK;
   hipStream_t st = ctx->c.stream;
   kzgx::GenTables g;

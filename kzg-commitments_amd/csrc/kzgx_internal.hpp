@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <cstdlib>
 #include <vector>
 
 #include "../../include/kzg_gpu.h"
@@ -35,6 +36,13 @@
 namespace kzgx {
 
 int hip_fail(hipError_t e);
+
+// an on/off environment switch: set and starting with '1' (DESIGN.md lists
+// every variable the library reads)
+static bool env_is_1(const char* name) {
+  const char* e = std::getenv(name);
+  return e && e[0] == '1';
+}
 
 struct MsmWs {
   uint32_t *counts = nullptr, *offsets = nullptr, *cursors = nullptr, *entries = nullptr;

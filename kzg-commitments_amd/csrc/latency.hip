@@ -19,8 +19,6 @@
 #endif
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 // The product form: the chained (throughput) form by default -- measured
 // faster here than the latency-first f29_mul_lat (2^20 + 1 points 2.579 vs
 // 2.603 ms, 131 073: 0.691 vs 0.724 ms, profiles/r05_big_msm_*): an XYZZ
@@ -165,18 +163,18 @@ size_t xyzz_record_words(int curve) {
 // ~2 log2(nb) additions whatever the schedule, and a lone wave issues one
 // XYZZ addition in ~7 us (its ~2400 VALU instructions), so the schedule is
 // made wide: every level runs on as many waves as it has elements.
-//   k_lat_bucket_sums: thread t owns J = 2 buckets: R_t = B_{2t} + 2 B_{2t+1},
-//                      T_t = B_{2t} + B_{2t+1}  (nb / 2 threads)
-//   k_lat_fold1:       256-thread workgroup g over pairs t = 256 g + l:
-//                      V_g = sum_l R_l + J sum_l l T_l (suffix sums S_l of T
-//                      by a wave scan + the higher waves' totals, a tree),
-//                      T_g = sum_l T_l
-//   k_lat_fold2:       one wave over the NG = nb / 512 groups: V = sum_g V_g
-//                      + 256 J sum_g g T_g the same way, then the wave-uniform
-//                      affine conversion
+//   k_lat_bucket_sums: thread t owns J = 4 buckets: R_t = sum_j (j + 1)
+//                      B_{Jt+j}, T_t = sum_j B_{Jt+j}  (nb / 4 threads; the
+//                      bucket-aligned segments' k_lat_seg_sums forms the
+//                      pairs of J = 2 buckets instead)
+//   k_coop_fold:       a level over N pairs, V = sum_t R_t + J t T_t, 32 pairs
+//                      per workgroup and an 8-lane group per pair, every point
+//                      operation cooperative (coop.hpp); levels repeat until
+//                      one pair is left
+//   k_coop_finish:     the wave-uniform affine conversion
 // (k_msm_bucket_fold_wg's algebra: sum_t t T_t = sum_{t >= 1} S_t.)
-constexpr uint32_t BIG_RED_J = 2;
-constexpr uint32_t BIG_F1 = 256;  // pairs per fold-1 workgroup
+constexpr uint32_t BIG_RED_J = 2;  // buckets per pair at most: sizes the pair buffer
+constexpr uint32_t BIG_F1 = 256;   // the reduction takes whole blocks of this many pairs
 
 template <class C, uint32_t J>
 __global__ __launch_bounds__(256) void k_lat_bucket_sums(const uint32_t* __restrict__ offsets, uint32_t nb,
@@ -208,104 +206,6 @@ KZGX_DEV Xyzz<C> xyzz_shfl_down_w(const Xyzz<C>& p, int off) {
   return o;
 }
 
-template <class C>
-KZGX_DEV Xyzz<C> xyzz_dbl_pow2(Xyzz<C> p, uint32_t m) {  // m p, m a power of two
-#pragma unroll 1
-  for (; m > 1; m >>= 1) p = xyzz_dbl_impl<C>(p);
-  return p;
-}
-
-// inclusive suffix sums over the wave's lanes < n (lanes >= n: infinity)
-template <class C>
-KZGX_DEV Xyzz<C> wave_suffix(Xyzz<C> S, uint32_t lane, uint32_t n) {
-#pragma unroll 1
-  for (uint32_t o = 1; o < n; o <<= 1) {
-    const Xyzz<C> x = xyzz_shfl_down_w<C>(S, (int)o);
-    if (lane + o < n) S = xyzz_add_impl<C>(S, x);
-  }
-  return S;
-}
-// sum over the wave's lanes < n, landing in lane 0
-template <class C>
-KZGX_DEV Xyzz<C> wave_total(Xyzz<C> U, uint32_t n) {
-#pragma unroll 1
-  for (uint32_t o = 32; o >= 1; o >>= 1)
-    if (o < n) U = xyzz_add_impl<C>(U, xyzz_shfl_down_w<C>(U, (int)o));
-  return U;
-}
-
-// workgroups g < NG: V_g = sum_l R_l + J sum_l l T_l over the group's 256
-// pairs.  Workgroups NG + g: T'_g = 512 T_g (J BIG_F1 = 512), the group
-// total scaled for the second level, on its own CU so that its 9 doublings
-// run beside V_g's chain instead of after it (k_lat_fold2 then needs none).
-template <class C>
-__global__ __launch_bounds__(BIG_F1) void k_lat_fold1(const uint32_t* __restrict__ rt, uint32_t NG,
-                                                      uint32_t* __restrict__ vt) {
-  constexpr int XW = xyzz_words<C>();
-  constexpr uint32_t NW = BIG_F1 / 64;
-  static_assert(NW == 4, "k_lat_fold1: four waves");
-  __shared__ uint32_t lds[NW * XW];
-  const uint32_t l = threadIdx.x, lane = l & 63, wv = l >> 6;
-  if (blockIdx.x >= NG) {
-    const uint32_t g = blockIdx.x - NG;
-    Xyzz<C> T = wave_total<C>(xyzz_load<C>(rt + ((size_t)g * BIG_F1 + l) * 2 * XW + XW), 64);
-    if (lane == 0) xyzz_store<C>(lds + wv * XW, T);
-    __syncthreads();
-    if (l != 0) return;
-    T = xyzz_add_impl<C>(xyzz_add_impl<C>(T, xyzz_load<C>(lds + XW)),
-                         xyzz_add_impl<C>(xyzz_load<C>(lds + 2 * XW), xyzz_load<C>(lds + 3 * XW)));
-    xyzz_store<C>(vt + (size_t)g * 2 * XW + XW, xyzz_dbl_pow2<C>(T, BIG_RED_J * BIG_F1));
-    return;
-  }
-  const uint32_t* src = rt + ((size_t)blockIdx.x * BIG_F1 + l) * 2 * XW;
-  const Xyzz<C> R = xyzz_load<C>(src);
-  Xyzz<C> S = wave_suffix<C>(xyzz_load<C>(src + XW), lane, 64);
-  if (lane == 0) xyzz_store<C>(lds + wv * XW, S);
-  __syncthreads();
-#pragma unroll 1
-  for (uint32_t w = wv + 1; w < NW; w++) S = xyzz_add_impl<C>(S, xyzz_load<C>(lds + w * XW));
-  __syncthreads();  // lds is reused below
-  Xyzz<C> U = R;
-  if (l > 0) U = xyzz_add_impl<C>(U, xyzz_dbl_pow2<C>(S, BIG_RED_J));
-  U = wave_total<C>(U, 64);
-  if (lane == 0) xyzz_store<C>(lds + wv * XW, U);
-  __syncthreads();
-  // (U0 + U1) + (U2 + U3): waves 0 and 2 in parallel, then thread 0
-  if (l == 128) xyzz_store<C>(lds + 2 * XW, xyzz_add_impl<C>(U, xyzz_load<C>(lds + 3 * XW)));
-  if (l == 0) U = xyzz_add_impl<C>(U, xyzz_load<C>(lds + XW));
-  __syncthreads();
-  if (l != 0) return;
-  xyzz_store<C>(vt + (size_t)blockIdx.x * 2 * XW, xyzz_add_impl<C>(U, xyzz_load<C>(lds + 2 * XW)));
-}
-
-template <class C>
-__global__ __launch_bounds__(64) void k_lat_fold2(const uint32_t* __restrict__ vt, uint32_t NG,
-                                                  uint32_t* __restrict__ out, uint32_t* __restrict__ out_inf) {
-  constexpr int XW = xyzz_words<C>();
-  const uint32_t lane = threadIdx.x;
-  Xyzz<C> V = xyzz_inf<C>(), S = xyzz_inf<C>();
-  if (lane < NG) {
-    V = xyzz_load<C>(vt + (size_t)lane * 2 * XW);
-    S = xyzz_load<C>(vt + (size_t)lane * 2 * XW + XW);  // already 512 T_g
-  }
-  S = wave_suffix<C>(S, lane, NG);
-  if (lane > 0 && lane < NG) V = xyzz_add_impl<C>(V, S);
-  V = wave_total<C>(V, NG);
-  Xyzz<C> v;
-#pragma unroll
-  for (int k = 0; k < C::Fp29::L; k++) {
-    v.X.v[k] = __builtin_amdgcn_readfirstlane(V.X.v[k]);
-    v.Y.v[k] = __builtin_amdgcn_readfirstlane(V.Y.v[k]);
-    v.ZZ.v[k] = __builtin_amdgcn_readfirstlane(V.ZZ.v[k]);
-    v.ZZZ.v[k] = __builtin_amdgcn_readfirstlane(V.ZZZ.v[k]);
-  }
-  Affine<C> a;
-  const bool fin = xyzz_to_affine_impl<C, true>(v, a);
-  if (lane != 0) return;
-  affine_to_canonical<C>(out, a, fin);
-  *out_inf = fin ? 0u : 1u;
-}
-
 size_t big_reduce_rt_bytes(int curve, uint32_t nb) {
   const size_t xb = 4 * (curve == KZGX_CURVE_BN254 ? xyzz_words<BN254G1>() : xyzz_words<BLS12381G1>());
   const size_t T1 = nb / BIG_RED_J;
@@ -321,20 +221,7 @@ size_t big_reduce_rt_bytes(int curve, uint32_t nb) {
 //   workgroups NGo + b:  T'_b = 2^(5 + JLOG) sum_l T_l, beside V_b's chain,
 // so the next level sees pairs (V_b, T'_b) with JLOG = 0.  Every point op is
 // one cooperative addition / doubling (~1/3 of a lone lane's latency).
-// the fold's point ops: cooperative, or (LONE, A/B and debugging) every
-// lane of the group running the lone-lane form
-template <class C, bool LONE>
-KZGX_DEV Xyzz<C> cadd(const Xyzz<C>& a, const Xyzz<C>& b, uint32_t* sc, int j) {
-  if constexpr (LONE) return xyzz_add_impl<C>(a, b);
-  else return coop_add<C>(a, b, sc, j);
-}
-template <class C, bool LONE>
-KZGX_DEV Xyzz<C> cdbl(const Xyzz<C>& a, uint32_t* sc, int j) {
-  if constexpr (LONE) return xyzz_dbl_impl<C>(a);
-  else return coop_dbl<C>(a, sc, j);
-}
-
-template <class C, int JLOG, bool LONE>
+template <class C, int JLOG>
 __global__ __launch_bounds__(256) void k_coop_fold(const uint32_t* __restrict__ in, uint32_t N, uint32_t NGo,
                                                    uint32_t* __restrict__ out) {
   using F = typename C::Fp29;
@@ -351,15 +238,15 @@ __global__ __launch_bounds__(256) void k_coop_fold(const uint32_t* __restrict__ 
   if (tpath) {
     Xyzz<C> T = idx < N ? xyzz_load<C>(src + XW) : xyzz_inf<C>();
 #pragma unroll 1
-    for (int o = 4; o >= 1; o >>= 1) T = cadd<C, LONE>(T, xyzz_shfl_down_w<C>(T, 8 * o), my, j);
+    for (int o = 4; o >= 1; o >>= 1) T = coop_add<C>(T, xyzz_shfl_down_w<C>(T, 8 * o), my, j);
     if ((t & 63) == 0) xyzz_store<C>(wt + wv * XW, T);
     __syncthreads();
     if (t >= 16) return;
     // groups 0 and 1 of wave 0: (wt0 + wt1), (wt2 + wt3); then group 0 adds
-    T = cadd<C, LONE>(xyzz_load<C>(wt + (2 * g) * XW), xyzz_load<C>(wt + (2 * g + 1) * XW), my, j);
-    T = cadd<C, LONE>(T, xyzz_shfl_down_w<C>(T, 8), my, j);
+    T = coop_add<C>(xyzz_load<C>(wt + (2 * g) * XW), xyzz_load<C>(wt + (2 * g + 1) * XW), my, j);
+    T = coop_add<C>(T, xyzz_shfl_down_w<C>(T, 8), my, j);
 #pragma unroll 1
-    for (int d = 0; d < 5 + JLOG; d++) T = cdbl<C, LONE>(T, my, j);
+    for (int d = 0; d < 5 + JLOG; d++) T = coop_dbl<C>(T, my, j);
     if (t == 0) xyzz_store<C>(out + (size_t)b * 2 * XW + XW, T);
     return;
   }
@@ -368,31 +255,31 @@ __global__ __launch_bounds__(256) void k_coop_fold(const uint32_t* __restrict__ 
 #pragma unroll 1
   for (uint32_t o = 1; o < 8; o <<= 1) {
     const Xyzz<C> x = xyzz_shfl_down_w<C>(S, (int)(8 * o));
-    if (gw + o < 8) S = cadd<C, LONE>(S, x, my, j);
+    if (gw + o < 8) S = coop_add<C>(S, x, my, j);
   }
   if ((t & 63) == 0) xyzz_store<C>(wt + wv * XW, S);
   __syncthreads();
 #pragma unroll 1
-  for (uint32_t w = wv + 1; w < 4; w++) S = cadd<C, LONE>(S, xyzz_load<C>(wt + w * XW), my, j);
+  for (uint32_t w = wv + 1; w < 4; w++) S = coop_add<C>(S, xyzz_load<C>(wt + w * XW), my, j);
   __syncthreads();  // wt is reused below
   Xyzz<C> U = R;
   if (g > 0) {
 #pragma unroll 1
-    for (int d = 0; d < JLOG; d++) S = cdbl<C, LONE>(S, my, j);
-    U = cadd<C, LONE>(U, S, my, j);
+    for (int d = 0; d < JLOG; d++) S = coop_dbl<C>(S, my, j);
+    U = coop_add<C>(U, S, my, j);
   }
 #pragma unroll 1
-  for (int o = 4; o >= 1; o >>= 1) U = cadd<C, LONE>(U, xyzz_shfl_down_w<C>(U, 8 * o), my, j);
+  for (int o = 4; o >= 1; o >>= 1) U = coop_add<C>(U, xyzz_shfl_down_w<C>(U, 8 * o), my, j);
   if ((t & 63) == 0) xyzz_store<C>(wt + wv * XW, U);
   __syncthreads();
   if (t < 8 || (t >= 128 && t < 136)) {  // group 0 of waves 0 and 2
     const Xyzz<C> o = xyzz_load<C>(wt + (wv + 1) * XW);
-    U = cadd<C, LONE>(U, o, my, j);
+    U = coop_add<C>(U, o, my, j);
     if (t == 128) xyzz_store<C>(wt + 2 * XW, U);
   }
   __syncthreads();
   if (t >= 8) return;
-  U = cadd<C, LONE>(U, xyzz_load<C>(wt + 2 * XW), my, j);
+  U = coop_add<C>(U, xyzz_load<C>(wt + 2 * XW), my, j);
   if (t == 0) xyzz_store<C>(out + (size_t)b * 2 * XW, U);
 }
 
@@ -494,20 +381,9 @@ int coop_selftest(int curve, const uint32_t* d_tab, uint32_t n_pts, uint32_t* d_
   return KZGX_OK;
 }
 
-// A/B-only kernels (the lone-lane fold forms behind KZGX_COOP_LONE and
-// KZGX_BIG_LONEFOLD) are compiled only into variant builds
-// (make variant VFLAGS=-DKZGX_AB_VARIANTS): the dispatcher never reaches
-// them otherwise, and they were a third of this object's compile time
 template <class C, int JLOG>
 static void coop_level(const uint32_t* in, uint32_t N, uint32_t NG, uint32_t* out, hipStream_t st) {
-#ifdef KZGX_AB_VARIANTS
-  static const bool lone = std::getenv("KZGX_COOP_LONE") != nullptr;
-  if (lone) {
-    hipLaunchKernelGGL((k_coop_fold<C, JLOG, true>), dim3(2 * NG), dim3(256), 0, st, in, N, NG, out);
-    return;
-  }
-#endif
-  hipLaunchKernelGGL((k_coop_fold<C, JLOG, false>), dim3(2 * NG), dim3(256), 0, st, in, N, NG, out);
+  hipLaunchKernelGGL((k_coop_fold<C, JLOG>), dim3(2 * NG), dim3(256), 0, st, in, N, NG, out);
 }
 
 // rt holds T1 pairs (R_t, T_t) weighted V = sum_t R_t + 2^jlog t T_t
@@ -544,18 +420,6 @@ static int big_reduce_impl(const uint32_t* d_offsets, uint32_t nb, const uint32_
                            uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st, uint32_t* xyzz_out) {
   const uint32_t T1 = nb / BIG_RED_J, NG = T1 / BIG_F1;
   if (NG < 1 || T1 % BIG_F1) return KZGX_ERR_INTERNAL;  // nb >= 512
-#ifdef KZGX_AB_VARIANTS
-  static const bool lone = std::getenv("KZGX_BIG_LONEFOLD") != nullptr;
-  if (lone && !xyzz_out && NG <= 64) {  // k_lat_fold2: one wave over the NG groups
-    uint32_t* vt = d_rt + (size_t)T1 * 2 * xyzz_words<C>();
-    hipLaunchKernelGGL((k_lat_bucket_sums<C, BIG_RED_J>), dim3((T1 + 255) / 256), dim3(256), 0, st, d_offsets, nb,
-                       d_bsum, d_rt);
-    hipLaunchKernelGGL(k_lat_fold1<C>, dim3(2 * NG), dim3(BIG_F1), 0, st, d_rt, NG, vt);
-    hipLaunchKernelGGL(k_lat_fold2<C>, dim3(1), dim3(64), 0, st, vt, NG, d_out, d_out_inf);
-    KZGX_TRY_HIP(hipGetLastError());
-    return KZGX_OK;
-  }
-#endif
   // 4 buckets per bucket-sum thread: half the pairs for the cooperative
   // levels (the first level then holds 2 waves per SIMD, not 4)
   const uint32_t T4 = nb / 4;
@@ -647,7 +511,6 @@ static int big_reduce_seg_impl(const uint32_t* d_seg_off, uint32_t* d_part, uint
                                hipStream_t st, uint32_t* xyzz_out) {
   const uint32_t T1 = nb / BIG_RED_J, NG = T1 / BIG_F1;
   if (NG < 1 || T1 % BIG_F1) return KZGX_ERR_INTERNAL;
-  uint32_t* vt = d_rt + (size_t)T1 * 2 * xyzz_words<C>();
   // pre-sum passes: as many as the largest possible bucket (s_ub partials)
   // could need; each exits at once unless some bucket has > LAT_MAXSEG
   for (uint64_t sp = 1; (s_ub + sp - 1) / sp > LAT_MAXSEG; sp *= 8)
@@ -660,19 +523,6 @@ static int big_reduce_seg_impl(const uint32_t* d_seg_off, uint32_t* d_part, uint
   else
     hipLaunchKernelGGL((k_lat_seg_sums<C, 4>), dim3((nb * 4 + 255) / 256), dim3(256), 0, st, d_seg_off, nb, d_part,
                        d_rt);
-  // the fold: group-cooperative levels (variant builds: KZGX_BIG_LONEFOLD,
-  // the lone-lane k_lat_fold1 / k_lat_fold2, A/B)
-#ifdef KZGX_AB_VARIANTS
-  static const bool lone = std::getenv("KZGX_BIG_LONEFOLD") != nullptr;
-  if (lone && !xyzz_out && NG <= 64) {  // k_lat_fold2: one wave over the NG groups
-    hipLaunchKernelGGL(k_lat_fold1<C>, dim3(2 * NG), dim3(BIG_F1), 0, st, d_rt, NG, vt);
-    hipLaunchKernelGGL(k_lat_fold2<C>, dim3(1), dim3(64), 0, st, vt, NG, d_out, d_out_inf);
-    KZGX_TRY_HIP(hipGetLastError());
-    return KZGX_OK;
-  }
-#else
-  (void)vt;
-#endif
   return coop_levels<C>(d_rt, T1, 1, d_out, d_out_inf, st, xyzz_out);
 }
 

@@ -1337,10 +1337,8 @@ static int bucket_reduce(Ctx* ctx, MsmWs& ws, size_t batch, hipStream_t st, uint
   // wavefronts per MSM are what fills the chip; from 256 MSMs the
   // one-wavefront fold + thread-per-MSM finish is faster (measured, BN254
   // c = 12: B = 128 wg +2.4%; B = 512 wave +2.8%; B = 2048 wave +6.7%,
-  // profiles/r02_s3_pip_fold_ab.json).  KZGX_PIP_WAVE_FOLD forces the
-  // wavefront form at every batch size (A/B).
-  static const bool fold_wave = std::getenv("KZGX_PIP_WAVE_FOLD") != nullptr;
-  if (T1 % FOLD_WG == 0 && batch < 256 && !fold_wave) {
+  // profiles/r02_s3_pip_fold_ab.json)
+  if (T1 % FOLD_WG == 0 && batch < 256) {
     hipLaunchKernelGGL((k_msm_bucket_fold_wg<C, J>), dim3((unsigned)batch), dim3(FOLD_WG), 0, st, ws.rt, T1, xyzz_out,
                        d_out, d_out_inf);
     KZGX_TRY_HIP(hipGetLastError());
@@ -1558,7 +1556,9 @@ static int msm_big_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t*
   const uint32_t per = 2048;
   const size_t nblk = (n + per - 1) / per;
   const uint32_t K = segment_len(ctx, emax);
-  static const bool one_pass = std::getenv("KZGX_BIG_ONEPASS") != nullptr;  // A/B: the one-pass sort + merge
+  // KZGX_BIG_ONEPASS (set at all; tests/test_gpu_env_hooks.py): the one-pass
+  // sort + called merge below, which otherwise needs an SRS above 2 M points
+  static const bool one_pass = std::getenv("KZGX_BIG_ONEPASS") != nullptr;
   if (!one_pass && (size_t)W * ctx->n_srs < ((size_t)1 << BigFine<CB>::IDX) && n <= (size_t)65535 * 1536) {
     const uint32_t per2 = big2_per<CB>();
     const size_t nblk2 = (n + per2 - 1) / per2;
@@ -1596,13 +1596,11 @@ static int msm_big_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t*
     // reduction (no merge, but measured 1.83 vs 1.31 ms of accumulation on
     // 2^20 + 1 points at the same VALU count and cache hit rate,
     // profiles/r05_big_msm_pmc.json -- an unexplained gap, left measured)
-    // (KZGX_BIG_SEGACC=0/1 pins it; by default bucket-aligned segments when K
-    // was cut to <= 32 to spread a smaller MSM: buckets then span ~20
-    // segments and the merge's chains dominate -- 131 073 points 0.64 vs
-    // 0.84 ms, while 2^20 + 1 points take 2.20 vs 2.62 ms with the merge)
-    static const char* seg_env = std::getenv("KZGX_BIG_SEGACC");
-    const bool seg_acc = seg_env ? seg_env[0] == '1' : K <= 32;
-    if (seg_acc) {
+    // (bucket-aligned segments when K was cut to <= 32 to spread a smaller
+    // MSM: buckets then span ~20 segments and the merge's chains dominate --
+    // 131 073 points 0.64 vs 0.84 ms, while 2^20 + 1 points take 2.20 vs
+    // 2.62 ms with the merge)
+    if (K <= 32) {
       KZGX_TRY(dev_alloc(ctx, (void**)&ws.tailk, (NB + 1) * 4, &ws.tailk_b));  // seg_off
       KZGX_TRY(dev_alloc(ctx, (void**)&ws.heads, s_ub * XB, &ws.heads_b));     // segment partials
       uint32_t* seg_off = ws.tailk;
@@ -1617,10 +1615,9 @@ static int msm_big_impl(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t*
       return big_reduce_seg(ctx->curve, seg_off, ws.heads, NB, (uint32_t)s_ub, flag, ws.rt, d_out, d_out_inf, st,
                             xyzz_out);
     }
-    static const bool merge_called = std::getenv("KZGX_BIG_MERGE_CALLED") != nullptr;  // A/B
     std::optional<ProfScope> reduce;
-    KZGX_TRY(accum_stage<C>(ctx, ws, 1, emax, NB, ctx->d_table_big, K, st, merge_called ? Merge::Called : Merge::Inline,
-                            "msm_accum", "msm_reduce", reduce));
+    KZGX_TRY(accum_stage<C>(ctx, ws, 1, emax, NB, ctx->d_table_big, K, st, Merge::Inline, "msm_accum", "msm_reduce",
+                            reduce));
     return big_reduce(ctx->curve, ws.offsets, NB, ws.bsum, ws.rt, d_out, d_out_inf, st, xyzz_out);
   }
   // the one-pass sort's per-block LDS histograms hold NB counters: not at

@@ -83,46 +83,6 @@ __global__ __launch_bounds__(256) void k_fixed_bases_from_table(const uint32_t* 
   if (w == 0) inf[i] = inf_src[i];
 }
 
-// M(w, i, j0 + j) = (2 (j0 + j) + 1) B[w][i], j < J (the odd multiples the
-// regular odd digits index, fixed_accum.hpp); thread per (w, i, block),
-// written at the table's strides (TabStrides)
-template <class C>
-__global__ __launch_bounds__(64) void k_fixed_multiples(const uint32_t* __restrict__ bases,
-                                                        const uint8_t* __restrict__ inf, uint32_t n, int W, uint32_t H,
-                                                        uint32_t J, uint64_t g0, uint64_t cnt, TabStrides ts,
-                                                        uint32_t* __restrict__ tab) {
-  constexpr int PW = packed_words<C>();
-  const uint64_t gl = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t nblk = H / J;
-  if (gl >= cnt) return;
-  const uint64_t g = g0 + gl;  // < W n nblk
-  const uint32_t blk = (uint32_t)(g % nblk);
-  const uint64_t wi = g / nblk;  // w * n + i
-  const uint32_t i = (uint32_t)(wi % n);
-  const uint32_t w = (uint32_t)(wi / n);
-  uint32_t* out = tab + (uint64_t)i * ts.is + (uint64_t)w * ts.ws + (uint64_t)blk * J * PW;
-  if (inf[i]) {  // never read: the MSM skips infinite SRS points
-    for (uint32_t j = 0; j < J * PW; j++) out[j] = 0;
-    return;
-  }
-  const Affine<C> B = packed_load<C>(bases + wi * PW);
-  Affine<C> B2;  // 2 B (!= O: B has order r > 2)
-  xyzz_to_affine<C>(xyzz_dbl<C>(xyzz_from_affine<C>(B)), B2);
-  const uint32_t k0 = 2 * blk * J + 1;
-  // acc = k0 B, left-to-right double-and-add
-  Xyzz<C> acc = xyzz_from_affine<C>(B);
-  for (int bit = 30 - __builtin_clz(k0); bit >= 0; bit--) {
-    acc = xyzz_dbl<C>(acc);
-    if ((k0 >> bit) & 1u) acc = xyzz_add_affine<C>(acc, B);
-  }
-  for (uint32_t j = 0; j < J; j++) {
-    if (j) acc = xyzz_add_affine<C>(acc, B2);
-    Affine<C> a;
-    xyzz_to_affine<C>(acc, a);  // (k0 + 2 j) B != O since k0 + 2 j < 2 H <= 2^17 < r
-    packed_store<C>(out + (size_t)j * PW, a);
-  }
-}
-
 // one wavefront per MSM: strided sums of the T partials, then a shuffle tree
 template <class C>
 __global__ __launch_bounds__(256) void k_fixed_reduce(const uint32_t* __restrict__ part, uint32_t T, uint32_t batch,
@@ -174,12 +134,8 @@ void fixed_reduce_launch(const uint32_t* part, uint32_t T, uint32_t batch, uint3
   // one wavefront per workgroup: a 131 073-point shard's 64:1 level over 48
   // wavefronts took 77 us against 116 us as 4-wave workgroups (r06
   // profiles; the waves of a workgroup do land on 4 different SIMDs,
-  // scripts/probe_simd.hip).  KZGX_REDUCE_WG256=1: the round-5 launch (A/B)
-  static const bool wg256 = std::getenv("KZGX_REDUCE_WG256") != nullptr;
-  if (!wg256)
-    hipLaunchKernelGGL(k_fixed_reduce<C>, dim3(batch), dim3(64), 0, st, part, T, batch, sums);
-  else
-    hipLaunchKernelGGL(k_fixed_reduce<C>, dim3((batch + 3) / 4), dim3(256), 0, st, part, T, batch, sums);
+  // scripts/probe_simd.hip)
+  hipLaunchKernelGGL(k_fixed_reduce<C>, dim3(batch), dim3(64), 0, st, part, T, batch, sums);
 }
 template <class C>
 void fixed_finish_launch(const uint32_t* sums, uint32_t batch, uint32_t* out, uint32_t* out_inf, uint32_t* xyzz_out,
@@ -194,22 +150,15 @@ template void fixed_finish_launch<BLS12381G1>(const uint32_t*, uint32_t, uint32_
 // --------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------
-constexpr uint32_t FIXED_J = 16;  // multiples per table-build thread
-
 // Table layout (TabStrides): point-major for c <= KZGX_FIXED_PM_MAX_C (the
 // few-large-MSM tables, walked point by point by k_fixed_accum_flat),
 // window-major above (profiles/r03_cfg5_table_layout.json,
-// r03_ab_point_major_cfg2.json).  kzgx_set_fixed_base_layout or
-// KZGX_FIXED_POINT_MAJOR=0/1 force one.
+// r03_ab_point_major_cfg2.json).  kzgx_set_fixed_base_layout forces one.
 #ifndef KZGX_FIXED_PM_MAX_C
 #define KZGX_FIXED_PM_MAX_C 12
 #endif
 static bool fixed_point_major(int c, int layout_req) {
-  // an explicit kzgx_set_fixed_base_layout(0/1) wins; the environment knob
-  // (A/B runs) only overrides the automatic choice
-  if (layout_req >= 0) return layout_req != 0;
-  static const char* e = std::getenv("KZGX_FIXED_POINT_MAJOR");
-  if (e && *e) return std::atoi(e) != 0;
+  if (layout_req >= 0) return layout_req != 0;  // kzgx_set_fixed_base_layout(0/1)
   return c <= KZGX_FIXED_PM_MAX_C;
 }
 
@@ -256,28 +205,10 @@ static int fixed_build_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_canon, s
                        d_bases, d_inf);
   ft.point_major = fixed_point_major(c, ft.layout_req);
   const TabStrides ts = fixed_strides<C>(ft.point_major, W, n, H);
-  // KZGX_TABLE_BUILD_SERIAL=1: the round-4 builder (one inversion per entry),
-  // for A/B runs of the batch-affine one (setup.hip)
-  static const bool serial = std::getenv("KZGX_TABLE_BUILD_SERIAL") && std::getenv("KZGX_TABLE_BUILD_SERIAL")[0] == '1';
-  if (!serial) {
+  // the batch-affine builder (setup.hip): one inversion per 16 entries
+  {
     ProfScope p(ctx, st, "fixed_build");
     KZGX_TRY(fixed_multiples_batch(ctx->curve, d_bases, d_inf, (uint32_t)n, W, (uint32_t)H, ts.is, ts.ws, ft.d, st));
-  } else {
-    const uint32_t J = (uint32_t)(H < FIXED_J ? H : FIXED_J);
-    const uint64_t tasks = (uint64_t)W * n * (H / J);
-    // bounded launches of <= 2^22 threads each, synchronised per slice so one
-    // setup never queues seconds of work behind a single dispatch
-    const uint64_t slice = 1ull << 22;
-    for (uint64_t s0 = 0; s0 < tasks; s0 += slice) {
-      const uint64_t cnt = tasks - s0 < slice ? tasks - s0 : slice;
-      {
-        ProfScope p(ctx, st, "fixed_build");
-        hipLaunchKernelGGL(k_fixed_multiples<C>, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, st, d_bases, d_inf,
-                           (uint32_t)n, W, (uint32_t)H, J, s0, cnt, ts, ft.d);
-      }
-      KZGX_TRY_HIP(hipGetLastError());
-      KZGX_TRY_HIP(hipStreamSynchronize(st));
-    }
   }
   // whether any SRS point of the prefix is infinite: when none is (every SRS
   // but a degenerate tau = 0 one), the accumulation kernels get no flag array

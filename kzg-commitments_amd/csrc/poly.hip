@@ -481,30 +481,16 @@ static int quotient_single_impl(Ctx* ctx, const uint32_t* d_coeffs, size_t n, si
   ProfScope prof(ctx, st, "quotient_single");
   // from QBIG_N coefficients a single opening spreads over the chip: a
   // degree-4096 create_proof(poly, z, 1) 0.69-0.73 ms with the one-wavefront
-  // kernel, 0.60-0.67 ms chip-wide (profiles/r03_latency_window.json;
-  // KZGX_QBIG_N overrides, for A/B)
-  static const size_t QBIG_N = [] {
-    const char* e = std::getenv("KZGX_QBIG_N");
-    return e && *e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)1u << 11;
-  }();
+  // kernel, 0.60-0.67 ms chip-wide (profiles/r03_latency_window.json)
+  constexpr size_t QBIG_N = (size_t)1u << 11;
   constexpr size_t QBIG_LANES = 1u << 18;  // 4096 wavefronts: 4 per SIMD
-  // one workgroup per opening from QWG_MIN to 2^14 coefficients
-  // (k_quotient_wg; KZGX_QWG_MIN overrides, 0 = never, for A/B)
-  static const size_t QWG_MIN = [] {
-    const char* e = std::getenv("KZGX_QWG_MIN");
-    return e && *e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)512;
-  }();
-  if (batch <= 4 && QWG_MIN && n >= QWG_MIN && n <= (1u << 14)) {
+  // one workgroup per opening from QWG_MIN to 2^14 coefficients (k_quotient_wg)
+  constexpr size_t QWG_MIN = 512;
+  if (batch <= 4 && n >= QWG_MIN && n <= (1u << 14)) {
     // 8 wavefronts (two per SIMD, half the chunk length): degree-4096 proof
-    // -9 us against 4 (profiles/r04_lat_ab_q64_qwg8.txt); KZGX_QWG_WAVES=4
-    // selects 4 (A/B)
-    static const bool w8 = !(std::getenv("KZGX_QWG_WAVES") && std::strtoul(std::getenv("KZGX_QWG_WAVES"), nullptr, 10) == 4);
-    if (w8)
-      hipLaunchKernelGGL((k_quotient_wg<FR, 8>), dim3((unsigned)batch), dim3(512), 0, st, d_coeffs, (uint32_t)n,
-                         cstride, d_z, d_q, qstride, d_y);
-    else
-      hipLaunchKernelGGL((k_quotient_wg<FR, 4>), dim3((unsigned)batch), dim3(256), 0, st, d_coeffs, (uint32_t)n,
-                         cstride, d_z, d_q, qstride, d_y);
+    // -9 us against 4 (profiles/r04_lat_ab_q64_qwg8.txt)
+    hipLaunchKernelGGL((k_quotient_wg<FR, 8>), dim3((unsigned)batch), dim3(512), 0, st, d_coeffs, (uint32_t)n,
+                       cstride, d_z, d_q, qstride, d_y);
     KZGX_TRY_HIP(hipGetLastError());
     return KZGX_OK;
   }

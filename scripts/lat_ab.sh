@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 TAG=$1
 shift
 VARIANTS=("$@")
-[[ ${#VARIANTS[@]} -eq 0 ]] && VARIANTS=(default KZGX_PIP_SEPARATE_MERGE=1 KZGX_PIP_SEPARATE_MERGE=1+KZGX_PIP_NO_FOLD_DIRECT=1 KZGX_PIP_KMIN=4)
+[[ ${#VARIANTS[@]} -eq 0 ]] && VARIANTS=(default)
 for v in "${VARIANTS[@]}"; do
   envs=()
   [[ $v != default ]] && IFS=+ read -r -a envs <<< "$v"

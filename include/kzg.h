@@ -120,6 +120,14 @@ class commit {
   G1& get_curve_point() { return curve_point; }
   std::vector<uint8_t> serialize();
   static commit deserialize(const std::vector<uint8_t>&);
+  /** Extension: deserialize() of every entry with one GPU pass for the whole
+   *  batch (kzgx_g1_check_batch; the host only parses octets).  Element k ==
+   *  deserialize(bytes[k]) when check_subgroup is false: a malformed or
+   *  off-curve octet decodes to infinity.  With check_subgroup a point outside
+   *  the prime-order subgroup (BLS12-381) decodes to infinity too.  valid[k]:
+   *  entry k was a well-formed point that passed the chosen checks. */
+  static std::vector<commit> deserialize_batch(const std::vector<std::vector<uint8_t>>& bytes,
+                                               bool check_subgroup = false, std::vector<bool>* valid = nullptr);
 };
 
 class proof {
@@ -131,6 +139,9 @@ class proof {
   G1& get_curve_point() { return curve_point; }
   std::vector<uint8_t> serialize();
   static proof deserialize(const std::vector<uint8_t>& bytes);
+  /** Extension: as commit::deserialize_batch. */
+  static std::vector<proof> deserialize_batch(const std::vector<std::vector<uint8_t>>& bytes,
+                                              bool check_subgroup = false, std::vector<bool>* valid = nullptr);
 };
 
 class trusted_setup {
@@ -139,6 +150,8 @@ class trusted_setup {
   size_t n = 0;
 
   G1 polyeval_G1(const std::vector<Fr>& P);
+  bool aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
+                  const std::vector<std::pair<Fr, Fr>>& points, bool checked, bool check_subgroup);
 
  public:
   /** random tau (std::random_device), [tau^i]G1 and [tau^i]G2 for
@@ -189,6 +202,17 @@ class trusted_setup {
    *  @throws std::invalid_argument on mismatched sizes */
   bool verify_proofs_aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
                                 const std::vector<std::pair<Fr, Fr>>& points);
+  /** Extension: the same behind a validation of every commit and proof
+   *  (kzgx_verify_aggregate_checked): canonical and on the curve, and with
+   *  check_subgroup in the prime-order subgroup; false as soon as one point
+   *  fails, whatever the pairing equation says. */
+  bool verify_proofs_aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
+                                const std::vector<std::pair<Fr, Fr>>& points, bool check_subgroup);
+  /** Extension: every installed G1 and G2 point is canonical, on its curve
+   *  and (subgroup) in the prime-order subgroup (kzgx_srs_check, on the
+   *  device).  trusted_setup(filename) tests on-curve only: call this after
+   *  loading a file you did not write. */
+  bool check_setup(bool subgroup = true);
   /** Extension: sum scalars[k] * points[k] on the GPU (kzgx_msm_g1_points).
    *  KZG commitments are additively homomorphic: the combination of
    *  commitments is the commitment of the combined polynomials.

@@ -354,9 +354,11 @@ int kzgx_msm_g1_points_device(kzgx_ctx* ctx, const void* d_points_xy, const void
  *   - 1 openings per call, else KZGX_ERR_ARG.
  *  Points are taken as canonical and on the curve, exactly as
  *   kzgx_verify_single_batch takes them (the C++ facade's deserialize
- *   validates).  Subgroup membership is NOT checked on BLS12-381: a caller
- *   who needs it must check before aggregating -- components outside the
- *   prime-order subgroup are the known weakness of random-combination checks.
+ *   validates).  Subgroup membership is NOT checked here on BLS12-381: a
+ *   caller who needs it uses kzgx_verify_aggregate_checked(_device) below, or
+ *   checks the points first with kzgx_g1_check_batch(_device) -- components
+ *   outside the prime-order subgroup are the known weakness of
+ *   random-combination checks.
  *  Equivalence: with explicit challenges the answer is a deterministic
  *   function of the inputs (the equation above, nothing else).  It equals the
  *   AND of the per-opening verifies when every opening is valid, and whenever
@@ -373,6 +375,41 @@ int kzgx_verify_aggregate(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* 
 int kzgx_verify_aggregate_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, const void* d_proofs,
                                  const void* d_proof_inf, const void* d_z, const void* d_y, const void* d_challenges,
                                  size_t count, void* d_ok, void* stream);
+
+
+/* ---- batched point validation, prime-order subgroup checks (extensions) ------
+ * One launch for any number of points, one lane per point.  With subgroup != 0
+ * a point must also lie in the order-r subgroup: on BN254 G1 the cofactor is 1
+ * and the flag adds nothing; on BLS12-381 G1 the test is [x^2]P = (beta x, -y)
+ * (exactly membership, DESIGN.md "Point validation"); on both G2 twists it is
+ * the definitional [r]Q = O.  The optimal ate pairing is bilinear only on
+ * G1 x G2, so the per-opening and the aggregated verify are the same predicate
+ * only for members. */
+/* ok[k] = 1 iff point k is canonical, on the curve and, if subgroup != 0, in the
+ * prime-order subgroup; infinite entries (flag or all-zero) pass.  count == 0 is KZGX_OK.
+ * is_inf may be NULL; at most KZGX_MSM_POINTS_MAX points per call, else KZGX_ERR_ARG. */
+int kzgx_g1_check_batch(kzgx_ctx* ctx, const uint64_t* xy, const int* is_inf, size_t count, int subgroup, int* ok);
+/* device pointers; d_ok count x uint32 and d_all_ok one uint32 (either may be NULL, not both);
+ * asynchronous on stream (NULL = the context's).  *d_all_ok = the AND of the
+ * flags (1 for count == 0), folded on the device. */
+int kzgx_g1_check_batch_device(kzgx_ctx* ctx, const void* d_xy, const void* d_is_inf, size_t count, int subgroup,
+                               void* d_ok, void* d_all_ok, void* stream);
+/* the same for G2 points (4 x W64 limbs each) */
+int kzgx_g2_check_batch(kzgx_ctx* ctx, const uint64_t* xy, const int* is_inf, size_t count, int subgroup, int* ok);
+/* every installed G1 / G2 SRS point, checked where it lies on the device (no copy of the SRS);
+ * *g2_ok = 1 when no G2 setup is installed; KZGX_ERR_NO_SRS without a G1 SRS */
+int kzgx_srs_check(kzgx_ctx* ctx, int subgroup, int* g1_ok, int* g2_ok);
+/* kzgx_verify_aggregate(_device) preceded by the G1 check of every commit and proof:
+ * *ok = 0 as soon as one of them fails, whatever the pairing equation says; otherwise the
+ * aggregate's answer.  The device form stays asynchronous (the AND is folded on the device).
+ * Arguments, limits and statuses as kzgx_verify_aggregate(_device). */
+int kzgx_verify_aggregate_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf,
+                                  const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* zs,
+                                  const uint64_t* ys, const uint64_t* challenges, size_t count, int subgroup, int* ok);
+int kzgx_verify_aggregate_checked_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                         const void* d_proofs, const void* d_proof_inf, const void* d_z,
+                                         const void* d_y, const void* d_challenges, size_t count, int subgroup,
+                                         void* d_ok, void* stream);
 
 #ifdef __cplusplus
 }

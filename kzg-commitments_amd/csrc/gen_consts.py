@@ -20,6 +20,59 @@ assert (1 - ((BN_P - 1) ** 3 + 2)) % BN_P == 0
 assert (BLS_GY**2 - BLS_GX**3 - 4) % BLS_P == 0
 
 
+# --------------------------------------------------------------------------
+# Prime-order subgroup test on G1 (subgroup.hip).  BN254 (Nogami): #E(Fp) =
+# p + 1 - t = r with t = 6u^2 + 1, cofactor 1, nothing to test.  BLS12-381:
+# #E(Fp) = r (x - 1)^2 / 3; phi(x, y) = (beta x, y) with beta a primitive
+# cube root of 1 in Fp acts on the order-r subgroup as a cube root of 1 mod r,
+# -x^2 for one beta and x^2 - 1 for the other.  The device test wants the
+# first: [x^2]P = -phi(P).
+# --------------------------------------------------------------------------
+assert BN_P + 1 - (6 * U * U + 1) == BN_R
+assert (BLS_P + 1 - (X + 1)) == BLS_R * ((X - 1) ** 2 // 3)
+
+
+def _g1_smul(p, P, k):
+    """[k]P on y^2 = x^3 + b (a = 0), affine, None = infinity"""
+    def add(A, B):
+        if A is None:
+            return B
+        if B is None:
+            return A
+        if A[0] == B[0]:
+            if (A[1] + B[1]) % p == 0:
+                return None
+            lam = 3 * A[0] * A[0] * pow(2 * A[1], -1, p) % p
+        else:
+            lam = (B[1] - A[1]) * pow(B[0] - A[0], -1, p) % p
+        x3 = (lam * lam - A[0] - B[0]) % p
+        return (x3, (lam * (A[0] - x3) - A[1]) % p)
+
+    R = None
+    for bit in bin(k)[2:]:
+        R = add(R, R)
+        if bit == "1":
+            R = add(R, P)
+    return R
+
+
+def _bls_beta():
+    g = 2
+    while pow(g, (BLS_P - 1) // 3, BLS_P) == 1:
+        g += 1
+    b = pow(g, (BLS_P - 1) // 3, BLS_P)
+    want = _g1_smul(BLS_P, (BLS_GX, BLS_GY), (-X * X) % BLS_R)
+    roots = [c for c in (b, b * b % BLS_P) if (c * BLS_GX % BLS_P, BLS_GY) == want]
+    assert len(roots) == 1
+    return roots[0]
+
+
+BLS_BETA = _bls_beta()
+assert BLS_BETA != 1 and pow(BLS_BETA, 3, BLS_P) == 1
+BLS_X2 = X * X  # the subgroup test's exponent: [x^2]P = (beta x, -y)
+assert (BLS_X2 * BLS_X2 - BLS_X2 + 1) == BLS_R
+
+
 def limbs(v, n):
     return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(n)]
 
@@ -298,6 +351,7 @@ def main():
         "  static constexpr uint32_t B[8] = %s;" % arr(mont(2, BN_P, 8), 8),
         "  static constexpr uint32_t GX29[9] = %s;  // radix-2^29 Montgomery" % arr29(mont29(BN_P - 1, BN_P, 9), 9),
         "  static constexpr uint32_t GY29[9] = %s;" % arr29(mont29(1, BN_P, 9), 9),
+        "  static constexpr bool COFACTOR_ONE = true;  // #E(Fp) = r: on the curve is in the subgroup",
         "};",
         "struct BLS12381G1 {",
         "  using Fp = BLS12381Fp;",
@@ -311,6 +365,11 @@ def main():
         "  static constexpr uint32_t B[12] = %s;" % arr(mont(4, BLS_P, 12), 12),
         "  static constexpr uint32_t GX29[14] = %s;" % arr29(mont29(BLS_GX, BLS_P, 14), 14),
         "  static constexpr uint32_t GY29[14] = %s;" % arr29(mont29(BLS_GY, BLS_P, 14), 14),
+        "  static constexpr bool COFACTOR_ONE = false;  // #E(Fp) = r (x - 1)^2 / 3",
+        "  // subgroup test [x^2]P = (beta x, -y): beta^3 = 1, (beta x, y) = [-x^2]P on the order-r subgroup",
+        "  static constexpr uint32_t BETA29[14] = %s;  // radix-2^29 Montgomery" % arr29(mont29(BLS_BETA, BLS_P, 14), 14),
+        "  static constexpr uint64_t X2[2] = {0x%016xull, 0x%016xull};  // x^2" % (BLS_X2 & (2**64 - 1), BLS_X2 >> 64),
+        "  static constexpr int X2_BITS = %d;" % BLS_X2.bit_length(),
         "};",
         pairing_struct("BN254", 9, 8),
         pairing_struct("BLS12381", 14, 12),

@@ -165,19 +165,26 @@ G2 to_g2(const uint64_t* w, bool inf) {
 // deserialize_ECP (util.cpp:98-115): anything that is not a valid on-curve
 // octet decodes to infinity.  The on-curve test runs on the GPU (g1_sum of
 // the single point is the identity iff the point is valid).
-G1 ecp_deserialize(const std::vector<uint8_t>& bytes) {
-  G1 inf;
-  if (bytes.size() < 4) return inf;
+// the octet's coordinates (not yet validated); false for a malformed octet
+bool ecp_parse(const std::vector<uint8_t>& bytes, G1& g) {
+  if (bytes.size() < 4) return false;
   uint32_t len;
   std::memcpy(&len, bytes.data(), 4);
   const size_t mb = mod_bytes();
-  if (len != 1 + 2 * mb || bytes.size() < 4 + len || bytes[4] != 0x04) return inf;
-  G1 g;
+  if (len != 1 + 2 * mb || bytes.size() < 4 + len || bytes[4] != 0x04) return false;
+  g = G1();
   g.inf = false;
   for (size_t k = 0; k < mb; k++) {
     g.x[k / 8] |= (uint64_t)bytes[4 + 1 + mb - 1 - k] << (8 * (k % 8));
     g.y[k / 8] |= (uint64_t)bytes[4 + 1 + 2 * mb - 1 - k] << (8 * (k % 8));
   }
+  return true;
+}
+
+G1 ecp_deserialize(const std::vector<uint8_t>& bytes) {
+  G1 inf;
+  G1 g;
+  if (!ecp_parse(bytes, g)) return inf;
   // validity: the GPU sums [P] alone and returns it canonically only if P is
   // a proper curve point (coordinates < p and y^2 = x^3 + b)
   const int nl = base_limbs();
@@ -189,6 +196,41 @@ G1 ecp_deserialize(const std::vector<uint8_t>& bytes) {
   int ok = 0;
   check(kzgx_g1_validate(default_ctx(), xy.data(), &ok), "kzgx_g1_validate");
   return ok ? g : inf;
+}
+
+// ecp_deserialize of every entry with ONE kzgx_g1_check_batch: the host only
+// parses octets.  Malformed octets and all-zero coordinates (not an octet
+// point: kzgx_g1_validate rejects them) go to the device as infinite entries
+// and are marked invalid here.
+std::vector<G1> ecp_deserialize_batch(const std::vector<std::vector<uint8_t>>& bytes, bool check_subgroup,
+                                      std::vector<bool>* valid) {
+  const size_t m = bytes.size();
+  const int nl = base_limbs();
+  std::vector<G1> res(m);
+  std::vector<uint64_t> xy(2 * nl * m + 1, 0);
+  std::vector<int> ok(m + 1, 0);
+  std::vector<bool> parsed(m, false);
+  for (size_t k = 0; k < m; k++) {
+    G1 g;
+    if (!ecp_parse(bytes[k], g)) continue;
+    uint64_t any = 0;
+    for (int i = 0; i < nl; i++) {
+      xy[2 * nl * k + i] = g.x[i];
+      xy[2 * nl * k + nl + i] = g.y[i];
+      any |= g.x[i] | g.y[i];
+    }
+    parsed[k] = any != 0;
+    res[k] = g;
+  }
+  if (m) check(kzgx_g1_check_batch(default_ctx(), xy.data(), nullptr, m, check_subgroup ? 1 : 0, ok.data()),
+               "kzgx_g1_check_batch");
+  if (valid) valid->assign(m, false);
+  for (size_t k = 0; k < m; k++) {
+    const bool good = parsed[k] && ok[k] != 0;
+    if (!good) res[k] = G1();
+    if (valid) (*valid)[k] = good;
+  }
+  return res;
 }
 
 }  // namespace
@@ -336,6 +378,20 @@ std::vector<uint8_t> commit::serialize() { return ecp_serialize(curve_point); }
 commit commit::deserialize(const std::vector<uint8_t>& b) { return commit(ecp_deserialize(b)); }
 std::vector<uint8_t> proof::serialize() { return ecp_serialize(curve_point); }
 proof proof::deserialize(const std::vector<uint8_t>& b) { return proof(ecp_deserialize(b)); }
+
+std::vector<commit> commit::deserialize_batch(const std::vector<std::vector<uint8_t>>& bytes, bool check_subgroup,
+                                              std::vector<bool>* valid) {
+  std::vector<commit> res;
+  for (const G1& g : ecp_deserialize_batch(bytes, check_subgroup, valid)) res.push_back(commit(g));
+  return res;
+}
+
+std::vector<proof> proof::deserialize_batch(const std::vector<std::vector<uint8_t>>& bytes, bool check_subgroup,
+                                            std::vector<bool>* valid) {
+  std::vector<proof> res;
+  for (const G1& g : ecp_deserialize_batch(bytes, check_subgroup, valid)) res.push_back(proof(g));
+  return res;
+}
 
 // ---- trusted_setup ----------------------------------------------------------
 trusted_setup::trusted_setup(int num_coeff) {
@@ -615,6 +671,22 @@ std::vector<bool> trusted_setup::verify_proofs(std::vector<commit>& commits, std
 
 bool trusted_setup::verify_proofs_aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
                                              const std::vector<std::pair<Fr, Fr>>& points) {
+  return aggregated(commits, proofs, points, false, false);
+}
+
+bool trusted_setup::verify_proofs_aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
+                                             const std::vector<std::pair<Fr, Fr>>& points, bool check_subgroup) {
+  return aggregated(commits, proofs, points, true, check_subgroup);
+}
+
+bool trusted_setup::check_setup(bool subgroup) {
+  int g1_ok = 0, g2_ok = 0;
+  check(kzgx_srs_check(ctx, subgroup ? 1 : 0, &g1_ok, &g2_ok), "kzgx_srs_check");
+  return g1_ok != 0 && g2_ok != 0;
+}
+
+bool trusted_setup::aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
+                               const std::vector<std::pair<Fr, Fr>>& points, bool checked, bool check_subgroup) {
   const size_t m = commits.size();
   if (proofs.size() != m || points.size() != m)
     throw std::invalid_argument("verify_proofs_aggregated: size mismatch");
@@ -637,8 +709,13 @@ bool trusted_setup::verify_proofs_aggregated(std::vector<commit>& commits, std::
     std::memcpy(&y[4 * k], points[k].second.v.data(), 32);
   }
   int ok = 0;
-  check(kzgx_verify_aggregate(ctx, c.data(), ci.data(), p.data(), pi.data(), z.data(), y.data(), nullptr, m, &ok),
-        "kzgx_verify_aggregate");
+  if (checked)
+    check(kzgx_verify_aggregate_checked(ctx, c.data(), ci.data(), p.data(), pi.data(), z.data(), y.data(), nullptr, m,
+                                        check_subgroup ? 1 : 0, &ok),
+          "kzgx_verify_aggregate_checked");
+  else
+    check(kzgx_verify_aggregate(ctx, c.data(), ci.data(), p.data(), pi.data(), z.data(), y.data(), nullptr, m, &ok),
+          "kzgx_verify_aggregate");
   return ok != 0;
 }
 

@@ -45,6 +45,10 @@ struct kzgx_ctx {
   uint32_t* d_g2tab = nullptr;
   size_t g2tab_b = 0;
   size_t g2tab_n = 0;  // points covered; 0 = stale
+  // per-point flags of the batched point checks, one buffer per workspace
+  // slot of c.ws (so per stream, as the MSM workspaces are)
+  uint32_t* d_chk[kzgx::KZGX_MAX_STREAMS] = {};
+  size_t chk_b[kzgx::KZGX_MAX_STREAMS] = {};
 
   // pinned, device-mapped host staging for the host-pointer entry points
   // (kzgx_msm_g1_batch, kzgx_prove_single_batch): inputs are copied into it
@@ -514,7 +518,8 @@ int kzgx_init_device(int curve, int device) {
       kzgx::warm_setup,      kzgx::warm_msm,        kzgx::warm_msm_fixed,   kzgx::warm_poly,
       kzgx::warm_srs,        kzgx::warm_pairing,    kzgx::warm_verify_wave, kzgx::warm_latency,
       kzgx::warm_fixed_bn_a, kzgx::warm_fixed_bn_b, kzgx::warm_fixed_bn_c,  kzgx::warm_fixed_bn_d,
-      kzgx::warm_fixed_bls_a, kzgx::warm_fixed_bls_b, kzgx::warm_fixed_bls_c, kzgx::warm_fixed_bls_d};
+      kzgx::warm_fixed_bls_a, kzgx::warm_fixed_bls_b, kzgx::warm_fixed_bls_c, kzgx::warm_fixed_bls_d,
+      kzgx::warm_subgroup};
   for (auto f : warm) KZGX_TRY(f(st));
   // the generator comb tables (per process, per device and curve)
   kzgx::GenTables g;
@@ -576,6 +581,8 @@ void kzgx_destroy(kzgx_ctx* ctx) {
                   c.d_poly_ws, c.d_poly_ws2, ctx->d_srs_canon, ctx->d_srs2_canon, c.d_g2_ws, ctx->d_vw, ctx->d_g2tab,
                   c.d_lift};
   for (void* p : bufs)
+    if (p) (void)hipFree(p);
+  for (void* p : ctx->d_chk)
     if (p) (void)hipFree(p);
   kzgx::fixed_free(&c);
   kzgx::fixed_free_table(c.fixed_def);
@@ -1666,9 +1673,123 @@ int kzgx_verify_aggregate_device(kzgx_ctx* ctx, const void* d_commits, const voi
   return kzgx_verify_single_batch_device(ctx, B, fl + 1, A, fl, zero, zero + 8, 1, d_ok, stream);
 }
 
-int kzgx_verify_aggregate(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, const uint64_t* proofs_xy,
-                          const int* proof_inf, const uint64_t* zs, const uint64_t* ys, const uint64_t* challenges,
-                          size_t count, int* ok) {
+// ---- batched point validation, prime-order subgroup checks (subgroup.hip) ---
+namespace {
+// the flags buffer of the workspace slot leased for this call's stream
+int chk_scratch(kzgx_ctx* ctx, const kzgx::WsLease& ws, size_t words, uint32_t** out) {
+  const size_t slot = (size_t)(ws.get() - ctx->c.ws);
+  KZGX_TRY(kzgx::dev_alloc(&ctx->c, (void**)&ctx->d_chk[slot], words * 4, &ctx->chk_b[slot]));
+  *out = ctx->d_chk[slot];
+  return KZGX_OK;
+}
+
+int check_batch_host(kzgx_ctx* ctx, bool g2, const uint64_t* xy, const int* is_inf, size_t count, int subgroup,
+                     int* ok) {
+  KZGX_TRY(activate(ctx));
+  if (count == 0) return KZGX_OK;
+  if (!xy || !ok || count > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  const size_t pb = (g2 ? 2 : 1) * point_words(ctx) * 4;
+  void *d_p, *d_f;
+  KZGX_TRY(stage(ctx, 0, count * pb, &d_p));
+  KZGX_TRY(stage(ctx, 1, count * 8, &d_f));
+  hipStream_t st = ctx->c.stream;
+  std::vector<uint32_t> f(count);
+  KZGX_TRY_HIP(hipMemcpyAsync(d_p, xy, count * pb, hipMemcpyHostToDevice, st));
+  if (is_inf) {
+    for (size_t k = 0; k < count; k++) f[k] = (uint32_t)(is_inf[k] != 0);
+    KZGX_TRY_HIP(hipMemcpyAsync(d_f, f.data(), count * 4, hipMemcpyHostToDevice, st));
+  }
+  uint32_t* d_ok = (uint32_t*)d_f + count;
+  KZGX_TRY((g2 ? kzgx::g2_check : kzgx::g1_check)(&ctx->c, (const uint32_t*)d_p, is_inf ? (const uint32_t*)d_f : nullptr,
+                                                  count, subgroup, d_ok, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(f.data(), d_ok, count * 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t k = 0; k < count; k++) ok[k] = (int)f[k];
+  return KZGX_OK;
+}
+}  // namespace
+
+int kzgx_g1_check_batch_device(kzgx_ctx* ctx, const void* d_xy, const void* d_is_inf, size_t count, int subgroup,
+                               void* d_ok, void* d_all_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if ((!d_ok && !d_all_ok) || (count > 0 && !d_xy) || count > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  if (count == 0) {
+    if (d_all_ok) KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)d_all_ok, 1, 1, st));
+    return KZGX_OK;
+  }
+  uint32_t* flags = (uint32_t*)d_ok;
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  if (!flags) KZGX_TRY(chk_scratch(ctx, ws, count, &flags));
+  KZGX_TRY(kzgx::g1_check(&ctx->c, (const uint32_t*)d_xy, (const uint32_t*)d_is_inf, count, subgroup, flags, st));
+  if (d_all_ok) KZGX_TRY(kzgx::flags_and(flags, count, (uint32_t*)d_all_ok, st));
+  return KZGX_OK;
+}
+
+int kzgx_g1_check_batch(kzgx_ctx* ctx, const uint64_t* xy, const int* is_inf, size_t count, int subgroup, int* ok) {
+  return check_batch_host(ctx, false, xy, is_inf, count, subgroup, ok);
+}
+
+int kzgx_g2_check_batch(kzgx_ctx* ctx, const uint64_t* xy, const int* is_inf, size_t count, int subgroup, int* ok) {
+  return check_batch_host(ctx, true, xy, is_inf, count, subgroup, ok);
+}
+
+int kzgx_srs_check(kzgx_ctx* ctx, int subgroup, int* g1_ok, int* g2_ok) {
+  KZGX_TRY(activate(ctx));
+  if (!g1_ok || !g2_ok) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  hipStream_t st = ctx->c.stream;
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const size_t n1 = ctx->c.n_srs, n2 = ctx->n_srs2, nmax = std::max(n1, n2);
+  uint32_t* f;
+  KZGX_TRY(chk_scratch(ctx, ws, nmax + 2, &f));
+  uint32_t* all = f + nmax;  // [G1, G2]
+  KZGX_TRY(kzgx::g1_check(&ctx->c, ctx->d_srs_canon, nullptr, n1, subgroup, f, st));
+  KZGX_TRY(kzgx::flags_and(f, n1, all, st));
+  KZGX_TRY(kzgx::g2_check(&ctx->c, ctx->d_srs2_canon, nullptr, n2, subgroup, f, st));
+  KZGX_TRY(kzgx::flags_and(f, n2, all + 1, st));  // n2 == 0: 1
+  uint32_t v[2] = {0, 0};
+  KZGX_TRY_HIP(hipMemcpyAsync(v, all, 8, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  *g1_ok = v[0] ? 1 : 0;
+  *g2_ok = v[1] ? 1 : 0;
+  return KZGX_OK;
+}
+
+int kzgx_verify_aggregate_checked_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                         const void* d_proofs, const void* d_proof_inf, const void* d_z,
+                                         const void* d_y, const void* d_challenges, size_t count, int subgroup,
+                                         void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (!d_ok || !d_challenges) return KZGX_ERR_ARG;
+  if (count > 0 && (!d_commits || !d_proofs || !d_z || !d_y)) return KZGX_ERR_ARG;
+  if (2 * count + 1 > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0 || ctx->n_srs2 < 2) return KZGX_ERR_NO_SRS;
+  hipStream_t st = pick(ctx, stream);
+  if (count == 0) {
+    KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)d_ok, 1, 1, st));
+    return KZGX_OK;
+  }
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  uint32_t* f;  // commit flags | proof flags | their AND
+  KZGX_TRY(chk_scratch(ctx, ws, 2 * count + 1, &f));
+  KZGX_TRY(kzgx::g1_check2(&ctx->c, (const uint32_t*)d_commits, (const uint32_t*)d_commit_inf, count,
+                           (const uint32_t*)d_proofs, (const uint32_t*)d_proof_inf, count, subgroup, f, st));
+  KZGX_TRY(kzgx::flags_and(f, 2 * count, f + 2 * count, st));
+  KZGX_TRY(kzgx_verify_aggregate_device(ctx, d_commits, d_commit_inf, d_proofs, d_proof_inf, d_z, d_y, d_challenges,
+                                        count, d_ok, stream));
+  return kzgx::flag_gate((uint32_t*)d_ok, f + 2 * count, st);
+}
+
+// the host-pointer aggregate: kzgx_verify_aggregate (checked = false) and
+// kzgx_verify_aggregate_checked share the staging and the drawn challenges
+static int verify_aggregate_host(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf,
+                                 const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* zs,
+                                 const uint64_t* ys, const uint64_t* challenges, size_t count, bool checked,
+                                 int subgroup, int* ok) {
   KZGX_TRY(activate(ctx));
   if (!ok) return KZGX_ERR_ARG;
   if (count > 0 && (!commits_xy || !proofs_xy || !zs || !ys)) return KZGX_ERR_ARG;
@@ -1708,13 +1829,32 @@ int kzgx_verify_aggregate(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* 
   KZGX_TRY_HIP(hipMemcpyAsync((char*)d_s + count * 64, challenges, count * 32, hipMemcpyHostToDevice, st));
   KZGX_TRY_HIP(hipMemcpyAsync(d_f, fl.data(), count * 8, hipMemcpyHostToDevice, st));
   uint32_t* d_ok = (uint32_t*)d_f + 2 * count;
-  KZGX_TRY(kzgx_verify_aggregate_device(ctx, d_c, d_f, d_p, (uint32_t*)d_f + count, d_s, (char*)d_s + count * 32,
-                                        (char*)d_s + count * 64, count, d_ok, nullptr));
+  if (checked)
+    KZGX_TRY(kzgx_verify_aggregate_checked_device(ctx, d_c, d_f, d_p, (uint32_t*)d_f + count, d_s,
+                                                  (char*)d_s + count * 32, (char*)d_s + count * 64, count, subgroup,
+                                                  d_ok, nullptr));
+  else
+    KZGX_TRY(kzgx_verify_aggregate_device(ctx, d_c, d_f, d_p, (uint32_t*)d_f + count, d_s, (char*)d_s + count * 32,
+                                          (char*)d_s + count * 64, count, d_ok, nullptr));
   uint32_t v = 0;
   KZGX_TRY_HIP(hipMemcpyAsync(&v, d_ok, 4, hipMemcpyDeviceToHost, st));
   KZGX_TRY_HIP(hipStreamSynchronize(st));
   *ok = v ? 1 : 0;
   return KZGX_OK;
+}
+
+int kzgx_verify_aggregate(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, const uint64_t* proofs_xy,
+                          const int* proof_inf, const uint64_t* zs, const uint64_t* ys, const uint64_t* challenges,
+                          size_t count, int* ok) {
+  return verify_aggregate_host(ctx, commits_xy, commit_inf, proofs_xy, proof_inf, zs, ys, challenges, count, false, 0,
+                               ok);
+}
+
+int kzgx_verify_aggregate_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf,
+                                  const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* zs,
+                                  const uint64_t* ys, const uint64_t* challenges, size_t count, int subgroup, int* ok) {
+  return verify_aggregate_host(ctx, commits_xy, commit_inf, proofs_xy, proof_inf, zs, ys, challenges, count, true,
+                               subgroup, ok);
 }
 
 }  // extern "C"

@@ -372,6 +372,19 @@ int pair2_wave(Ctx* ctx, const uint32_t* d_p, const uint32_t* d_p_inf, const uin
 // for a degenerate chain (rerun pair2_wave); d_q: Q_0 alone, d_q_inf: its flag
 int pair2_fused(Ctx* ctx, const uint32_t* d_p, const uint32_t* d_p_inf, const uint32_t* d_q, const uint32_t* d_q_inf,
                 const uint32_t* d_vw, uint32_t* d_ok, hipStream_t st);
+// batched point validation (subgroup.hip): d_ok[k] = 1 iff point k is
+// canonical, on the curve / twist and, with subgroup != 0, of order dividing
+// r; infinite entries (d_inf flag, may be NULL, or all-zero words) pass
+int g1_check(Ctx* ctx, const uint32_t* d_xy, const uint32_t* d_inf, size_t count, int subgroup, uint32_t* d_ok,
+             hipStream_t st);
+// two G1 arrays in one launch: d_ok holds count0 + count1 flags, the first array's first
+int g1_check2(Ctx* ctx, const uint32_t* d_xy0, const uint32_t* d_inf0, size_t count0, const uint32_t* d_xy1,
+              const uint32_t* d_inf1, size_t count1, int subgroup, uint32_t* d_ok, hipStream_t st);
+int g2_check(Ctx* ctx, const uint32_t* d_xy, const uint32_t* d_inf, size_t count, int subgroup, uint32_t* d_ok,
+             hipStream_t st);
+// *d_all = AND of count flags (1 when count == 0); *d_ok = *d_ok && *d_gate
+int flags_and(const uint32_t* d_flags, size_t count, uint32_t* d_all, hipStream_t st);
+int flag_gate(uint32_t* d_ok, const uint32_t* d_gate, hipStream_t st);
 int g1_sub(Ctx* ctx, const uint32_t* d_a, const uint32_t* d_a_inf, const uint32_t* d_b, const uint32_t* d_b_inf,
            uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st);
 

@@ -34,6 +34,8 @@ EXPORTS = [
     "kzgx_quotient_single_batch", "kzgx_shared_tables", "kzgx_release_cached_memory",
     "kzgx_partial_record_words", "kzgx_msm_g1_partial_device", "kzgx_g1_sum_partials_device",
     "kzgx_msm_g1_points", "kzgx_msm_g1_points_device", "kzgx_verify_aggregate", "kzgx_verify_aggregate_device",
+    "kzgx_g1_check_batch", "kzgx_g1_check_batch_device", "kzgx_g2_check_batch", "kzgx_srs_check",
+    "kzgx_verify_aggregate_checked", "kzgx_verify_aggregate_checked_device",
 ]
 
 _lib = None
@@ -133,6 +135,14 @@ def lib():
             "kzgx_msm_g1_points_device": (ctypes.c_int, [vp, vp, vp, vp, sz, vp, vp, vp]),
             "kzgx_verify_aggregate": (ctypes.c_int, [vp, u64p, intp, u64p, intp, u64p, u64p, u64p, sz, intp]),
             "kzgx_verify_aggregate_device": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+            "kzgx_g1_check_batch": (ctypes.c_int, [vp, u64p, intp, sz, ctypes.c_int, intp]),
+            "kzgx_g1_check_batch_device": (ctypes.c_int, [vp, vp, vp, sz, ctypes.c_int, vp, vp, vp]),
+            "kzgx_g2_check_batch": (ctypes.c_int, [vp, u64p, intp, sz, ctypes.c_int, intp]),
+            "kzgx_srs_check": (ctypes.c_int, [vp, ctypes.c_int, intp, intp]),
+            "kzgx_verify_aggregate_checked": (ctypes.c_int, [vp, u64p, intp, u64p, intp, u64p, u64p, u64p, sz,
+                                                             ctypes.c_int, intp]),
+            "kzgx_verify_aggregate_checked_device": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, sz, ctypes.c_int,
+                                                                    vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -600,3 +610,62 @@ class Context:
         """kzgx_verify_aggregate_device: device pointers, d_ok one uint32, enqueued on stream."""
         _chk(lib().kzgx_verify_aggregate_device(self.h, d_commits, d_commit_inf, d_proofs, d_proof_inf, d_z, d_y,
                                                 d_challenges, count, d_ok, stream), "kzgx_verify_aggregate_device")
+
+    # ---- batched point validation, prime-order subgroup checks ----
+    def _check_batch(self, fn, name, width, pts, inf, subgroup) -> np.ndarray:
+        xy = np.ascontiguousarray(pts, dtype=np.uint64).reshape(-1, width)
+        n = xy.shape[0]
+        f = None if inf is None else np.ascontiguousarray(inf, dtype=np.int32)
+        assert f is None or f.shape[0] == n
+        ok = np.zeros(n, dtype=np.int32)
+        _chk(fn(self.h, _p(xy) if n else None, None if f is None else f.ctypes.data_as(intp), n, int(bool(subgroup)),
+                ok.ctypes.data_as(intp)), name)
+        return ok.astype(bool)
+
+    def g1_check(self, pts, inf=None, subgroup: bool = False) -> np.ndarray:
+        """kzgx_g1_check_batch: per point, canonical + on the curve (+ in the order-r subgroup);
+        infinite entries (flag or all-zero) pass."""
+        return self._check_batch(lib().kzgx_g1_check_batch, "kzgx_g1_check_batch", 2 * self.w64, pts, inf, subgroup)
+
+    def g1_check_device(self, d_xy, d_inf, count, subgroup, d_ok, d_all_ok, stream=None):
+        """kzgx_g1_check_batch_device: device pointers (d_ok count x uint32, d_all_ok one uint32,
+        either may be None), enqueued on stream."""
+        _chk(lib().kzgx_g1_check_batch_device(self.h, d_xy, d_inf, count, int(bool(subgroup)), d_ok, d_all_ok, stream),
+             "kzgx_g1_check_batch_device")
+
+    def g2_check(self, pts, inf=None, subgroup: bool = False) -> np.ndarray:
+        """kzgx_g2_check_batch: the same for G2 points on the twist."""
+        return self._check_batch(lib().kzgx_g2_check_batch, "kzgx_g2_check_batch", 4 * self.w64, pts, inf, subgroup)
+
+    def srs_check(self, subgroup: bool = True):
+        """kzgx_srs_check: (g1_ok, g2_ok) over every installed SRS point, on the device."""
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _chk(lib().kzgx_srs_check(self.h, int(bool(subgroup)), ctypes.byref(a), ctypes.byref(b)), "kzgx_srs_check")
+        return bool(a.value), bool(b.value)
+
+    def verify_aggregate_checked(self, commits, proofs, zs, ys, challenges=None, commit_inf=None, proof_inf=None,
+                                 subgroup: bool = True) -> bool:
+        """verify_aggregate behind the G1 check of every commit and proof (False if one fails)."""
+        c = np.ascontiguousarray(commits, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        p = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        n = c.shape[0]
+        z = as_scalars(zs) if n else np.zeros((0, 4), dtype=np.uint64)
+        y = as_scalars(ys) if n else np.zeros((0, 4), dtype=np.uint64)
+        r = None if challenges is None else (as_scalars(challenges) if n else np.zeros((0, 4), dtype=np.uint64))
+        assert p.shape[0] == n and z.shape[0] == n and y.shape[0] == n and (r is None or r.shape[0] == n)
+        fc = None if commit_inf is None else np.ascontiguousarray(commit_inf, dtype=np.int32)
+        fp = None if proof_inf is None else np.ascontiguousarray(proof_inf, dtype=np.int32)
+        ok = ctypes.c_int(0)
+        _chk(lib().kzgx_verify_aggregate_checked(
+            self.h, _p(c) if n else None, None if fc is None else fc.ctypes.data_as(intp), _p(p) if n else None,
+            None if fp is None else fp.ctypes.data_as(intp), _p(z) if n else None, _p(y) if n else None,
+            None if r is None or not n else _p(r), n, int(bool(subgroup)), ctypes.byref(ok)),
+            "kzgx_verify_aggregate_checked")
+        return bool(ok.value)
+
+    def verify_aggregate_checked_device(self, d_commits, d_commit_inf, d_proofs, d_proof_inf, d_z, d_y, d_challenges,
+                                        count, subgroup, d_ok, stream=None):
+        """kzgx_verify_aggregate_checked_device: device pointers, d_ok one uint32, enqueued on stream."""
+        _chk(lib().kzgx_verify_aggregate_checked_device(self.h, d_commits, d_commit_inf, d_proofs, d_proof_inf, d_z,
+                                                        d_y, d_challenges, count, int(bool(subgroup)), d_ok, stream),
+             "kzgx_verify_aggregate_checked_device")

@@ -80,6 +80,11 @@ int curve();
  *  negative ordinal (a missing device fails at the next construction). */
 void set_device(int device);
 int device();
+/** Extension: the generator w of the size-2^log2n domain {w^i} that the
+ *  evaluation-form calls below work on (kzgx_domain_root): BLS12-381
+ *  7^((r-1)/2^log2n), log2n <= 32; BN254 2^((r-1)/2^log2n), log2n <= 2.
+ *  @throws std::invalid_argument beyond the field's 2-adicity */
+Fr domain_root(unsigned log2n);
 
 class blob {
  private:
@@ -107,6 +112,20 @@ class poly {
   long degree() const { return (long)data.size() - 1; }
   /** interpolate the blob's points (polyfit, util.cpp:172-184) on the GPU */
   static poly from_blob(blob blob);
+  /** Extension: the polynomial of degree < evals.size() with P(w^i) = evals[i],
+   *  w = domain_root(log2 size), by an inverse NTT on the GPU of device()
+   *  (kzgx_ntt); bit_reversed: evals[bit reversal of i] holds P(w^i).
+   *  Normalized as the constructor does.  BLS12-381 up to 2^22 values; BN254's
+   *  scalar field has no domain beyond 4 (from_blob interpolates there).
+   *  @throws std::invalid_argument if the size is not a power of two or
+   *          exceeds the curve's domain */
+  static poly from_evaluations(const std::vector<Fr>& evals, bool bit_reversed = false);
+  /** Extension: P on the whole size-2^log2n domain (forward NTT of the
+   *  zero-padded coefficients), element i = P(w^i), or with bit_reversed
+   *  element (bit reversal of i).
+   *  @throws std::invalid_argument if deg + 1 > 2^log2n or the size exceeds
+   *          the curve's domain */
+  std::vector<Fr> evaluate_domain(unsigned log2n, bool bit_reversed = false) const;
   std::vector<uint8_t> serialize();
   static poly deserialize(const std::vector<uint8_t>&);
 };
@@ -191,6 +210,19 @@ class trusted_setup {
   /** Extensions: batched commits / single-point openings in one GPU pass. */
   std::vector<commit> create_commits(const std::vector<kzg::poly>& polys);
   std::vector<proof> create_proofs(const kzg::poly& poly, const std::vector<long>& points);
+  /** Extension: commitments of polynomials given by their values on the
+   *  size-2^k domain (all vectors of that size), one GPU pass: inverse NTT,
+   *  then the batched MSM (kzgx_commit_evals_batch).  Equal to
+   *  create_commits of poly::from_evaluations of each vector.
+   *  @throws std::invalid_argument if the size is not a power of two, exceeds
+   *          the curve's domain, differs between vectors, or 2^k >= size() */
+  std::vector<commit> create_commits_from_evaluations(const std::vector<std::vector<Fr>>& evals,
+                                                      bool bit_reversed = false);
+  /** Extension: single-point openings at `points` (any scalars, domain points
+   *  included) of the polynomial given by `evals` (kzgx_prove_evals_batch).
+   *  @throws std::invalid_argument as create_commits_from_evaluations */
+  std::vector<proof> create_proofs_from_evaluations(const std::vector<Fr>& evals, const std::vector<Fr>& points,
+                                                    bool bit_reversed = false);
   /** Extension: many single-point verify_proof calls in one GPU pass;
    *  result k == verify_proof(commits[k], proofs[k], blob {points[k]}). */
   std::vector<bool> verify_proofs(std::vector<commit>& commits, std::vector<proof>& proofs,

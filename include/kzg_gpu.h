@@ -16,6 +16,12 @@
  *   kzgx_gen_srs_g1*        trusted_setup(int) G1 part, trusted_setup.cpp:21-74,123-135
  *   kzgx_load_srs_g1        trusted_setup(const string&) G1 part, trusted_setup.cpp:76-101
  *
+ * and add what the reference does not have (each marked "extension" below):
+ * aggregated verification, batched point validation, and the evaluation form --
+ * kzgx_ntt*, kzgx_commit_evals_batch*, kzgx_prove_evals_batch*: a radix-2 Fr NTT
+ * and commits / openings of polynomials given by their values on a power-of-two
+ * domain of roots of unity (BLS12-381 up to 2^22 values; BN254 only up to 4).
+ *
  * Conventions
  *   - plain pointers and sizes only; no torch / HIP types in signatures
  *     (streams are passed as void*, NULL = the context's own stream);
@@ -410,6 +416,64 @@ int kzgx_verify_aggregate_checked_device(kzgx_ctx* ctx, const void* d_commits, c
                                          const void* d_proofs, const void* d_proof_inf, const void* d_z,
                                          const void* d_y, const void* d_challenges, size_t count, int subgroup,
                                          void* d_ok, void* stream);
+
+/* ---- evaluation form (extensions) -------------------------------------------------
+ * Polynomials given by their values on the size-2^k domain of roots of unity
+ * {w^i}, w = kzgx_domain_root(curve, k), instead of by monomial coefficients:
+ * a batched radix-2 NTT over Fr, and commits / single-point openings that run
+ * the inverse NTT into context workspace and hand the coefficients to the
+ * kzgx_msm_g1_batch_device / kzgx_prove_single_batch_device pipelines as they
+ * are.  No reference counterpart.
+ *  Domain: BLS12-381's r - 1 is divisible by 2^32, w = 7^((r-1)/2^k); BN254
+ *   (Nogami)'s r - 1 only by 4, w = 2^((r-1)/2^k), so there the feature stops
+ *   at n = 4 and kzgx_poly_interpolate remains the way from values to
+ *   coefficients.
+ *  forward: out[i] = sum_j in[j] w^(i j);  inverse (KZGX_NTT_INVERSE):
+ *   out[j] = n^-1 sum_i in[i] w^(-i j).  The coefficient side is always in
+ *   natural order.  With KZGX_NTT_BITREV the evaluation side (forward output,
+ *   inverse input) is indexed by the k-bit reversal of i, the order
+ *   data-availability blobs use.  Scalars are canonical in and out.
+ *  Transforms up to 2^KZGX_NTT_TILE_LOG2 run in one pass out of LDS, larger
+ *   ones in two passes through a workspace of batch x n scalars.
+ *  Statuses: log2n > kzgx_ntt_max_log2(curve), a stride smaller than n (except
+ *   eval_stride == 0 below), an unknown flag bit: KZGX_ERR_ARG; 2^log2n larger
+ *   than the installed SRS: KZGX_ERR_DEGREE; no SRS: KZGX_ERR_NO_SRS;
+ *   batch == 0: KZGX_OK. */
+#define KZGX_NTT_MAX_LOG2 22
+#define KZGX_NTT_TILE_LOG2 12
+#define KZGX_NTT_INVERSE 1
+#define KZGX_NTT_BITREV 2
+/* largest log2 n the curve's scalar field allows, capped at KZGX_NTT_MAX_LOG2:
+ * BLS12-381 22, BN254 2; -1 for an unknown curve.  Host arithmetic, no device. */
+int kzgx_ntt_max_log2(int curve);
+/* the domain generator w of order 2^log2n, canonical 4 x uint64.  Host
+ * arithmetic, no device; valid up to the field's 2-adicity (BLS12-381: 32,
+ * BN254: 2), KZGX_ERR_ARG beyond */
+int kzgx_domain_root(int curve, unsigned log2n, uint64_t* root);
+/* batch transforms of n = 2^log2n scalars, in[b * n + i]; host pointers (in == out allowed) */
+int kzgx_ntt(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, size_t batch, int flags, uint64_t* out);
+/* device pointers, asynchronous on stream (NULL = the context's); transform b
+ * at d_in + b * in_stride scalars, written to d_out + b * out_stride scalars;
+ * scalars between the transforms are neither read nor written.  d_in == d_out
+ * is allowed (with equal strides) */
+int kzgx_ntt_device(kzgx_ctx* ctx, const void* d_in, size_t in_stride, void* d_out, size_t out_stride,
+                    unsigned log2n, size_t batch, int flags, void* stream);
+/* commit_k = MSM(inverse NTT of evals_k, SRS): bit-exact with committing to
+ * the interpolant.  flags: 0 or KZGX_NTT_BITREV.  The evaluations are only read. */
+int kzgx_commit_evals_batch(kzgx_ctx* ctx, const uint64_t* evals, unsigned log2n, size_t batch, int flags,
+                            uint64_t* out_xy, int* out_is_inf);
+int kzgx_commit_evals_batch_device(kzgx_ctx* ctx, const void* d_evals, unsigned log2n, size_t batch,
+                                   size_t eval_stride, int flags, void* d_out_xy, void* d_out_is_inf,
+                                   void* stream);
+/* single-point openings of polynomials given by evaluations; eval_stride == 0:
+ * one shared polynomial.  z may be any scalar, a domain point included;
+ * y_k = P_k(z_k) (d_y / out_y may be NULL).  flags: 0 or KZGX_NTT_BITREV */
+int kzgx_prove_evals_batch(kzgx_ctx* ctx, const uint64_t* evals, unsigned log2n, size_t eval_stride,
+                           const uint64_t* zs, size_t batch, int flags, uint64_t* out_xy, int* out_is_inf,
+                           uint64_t* out_y);
+int kzgx_prove_evals_batch_device(kzgx_ctx* ctx, const void* d_evals, unsigned log2n, size_t eval_stride,
+                                  const void* d_z, size_t batch, int flags, void* d_out_xy,
+                                  void* d_out_is_inf, void* d_y, void* stream);
 
 #ifdef __cplusplus
 }

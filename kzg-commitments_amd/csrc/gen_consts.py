@@ -158,6 +158,57 @@ def mont29(v, m, L):
 
 
 # --------------------------------------------------------------------------
+# Radix-2 NTT domains of the scalar fields (ntt.hip).  r - 1 = 2^s * odd; the
+# size-2^k domain (k <= s) is generated by g^((r - 1) / 2^k) for a quadratic
+# non-residue g, so the root has order exactly 2^k.  BLS12-381: s = 32, g = 7;
+# BN254 (Nogami): s = 2, g = 2.
+# --------------------------------------------------------------------------
+def two_adicity(r):
+    s = 0
+    while (r - 1) >> s & 1 == 0:
+        s += 1
+    return s
+
+
+NTT_GEN = {"BN254": 2, "BLS12381": 7}
+
+
+def domain_root(name, k):
+    r = BN_R if name == "BN254" else BLS_R
+    assert k <= two_adicity(r)
+    return pow(NTT_GEN[name], (r - 1) >> k, r)
+
+
+assert two_adicity(BLS_R) == 32 and two_adicity(BN_R) == 2
+assert all(pow(NTT_GEN[n], (r - 1) // 2, r) == r - 1 for n, r in (("BN254", BN_R), ("BLS12381", BLS_R)))
+assert domain_root("BLS12381", 32) == 0x16A2A19EDFE81F20D09B681922C813B4B63683508C2280B93829971F439F0D2B
+assert domain_root("BN254", 2) == 0x9366C4800000000555150000000000122400000000000015
+assert domain_root("BN254", 1) == BN_R - 1
+
+
+def ntt_struct(name):
+    """domain roots w_k (canonical and Montgomery) and 2^-k (Montgomery), k = 0..2-adicity"""
+    r = BN_R if name == "BN254" else BLS_R
+    s = two_adicity(r)
+
+    def rows(vals):
+        return "{\n" + ",\n".join("      " + arr(v, 8) for v in vals) + "}"
+
+    roots = [domain_root(name, k) for k in range(s + 1)]
+    return "\n".join([
+        "struct %sFrNtt {" % name,
+        "  static constexpr int TWO_ADICITY = %d;  // r - 1 = 2^TWO_ADICITY * odd" % s,
+        "  // w_k = %d^((r - 1) / 2^k), of order exactly 2^k; canonical" % NTT_GEN[name],
+        "  static constexpr uint32_t ROOT[%d][8] = %s;" % (s + 1, rows(roots)),
+        "  // the same in Montgomery form (the device twiddle table is built from these)",
+        "  static constexpr uint32_t ROOT_M[%d][8] = %s;" % (s + 1, rows(mont(v, r, 8) for v in roots)),
+        "  // 2^-k in Montgomery form (the inverse transform's scale)",
+        "  static constexpr uint32_t NINV_M[%d][8] = %s;" % (s + 1, rows(mont(pow(1 << k, -1, r), r, 8) for k in range(s + 1))),
+        "};",
+    ])
+
+
+# --------------------------------------------------------------------------
 # G2 / pairing constants (verify path: trusted_setup.cpp:123-135, 176-201,
 # 230-254).  Fp2 = Fp[i]/(i^2+1), xi = 1 + i, Fp6 = Fp2[v]/(v^3 - xi),
 # Fp12 = Fp6[w]/(w^2 - v).  The twist type is selected by group order: the
@@ -373,6 +424,8 @@ def main():
         "};",
         pairing_struct("BN254", 9, 8),
         pairing_struct("BLS12381", 14, 12),
+        ntt_struct("BN254"),
+        ntt_struct("BLS12381"),
         "}  // namespace kzgx",
         "",
     ]

@@ -343,6 +343,50 @@ poly poly::from_blob(blob b) {
   return poly(P);
 }
 
+// ---- evaluation form (extensions) --------------------------------------------
+namespace {
+// log2 of a power-of-two size within the selected curve's NTT domain
+unsigned domain_log2(size_t size, const char* where) {
+  unsigned k = 0;
+  while (((size_t)1 << k) < size) k++;
+  if (size == 0 || ((size_t)1 << k) != size) throw std::invalid_argument(std::string(where) + ": size is not a power of two");
+  if ((int)k > kzgx_ntt_max_log2(g_curve))
+    throw std::invalid_argument(std::string(where) + ": size exceeds the curve's power-of-two domain");
+  return k;
+}
+
+std::vector<Fr> unflat(const std::vector<uint64_t>& w) {
+  std::vector<Fr> out(w.size() / 4);
+  for (size_t i = 0; i < out.size(); i++) std::memcpy(out[i].v.data(), &w[4 * i], 32);
+  return out;
+}
+}  // namespace
+
+Fr domain_root(unsigned log2n) {
+  Fr w;
+  check(kzgx_domain_root(g_curve, log2n, w.v.data()), "kzgx_domain_root");
+  return w;
+}
+
+poly poly::from_evaluations(const std::vector<Fr>& evals, bool bit_reversed) {
+  const unsigned k = domain_log2(evals.size(), "from_evaluations");
+  auto e = flat(evals);
+  check(kzgx_ntt(default_ctx(), e.data(), k, 1, KZGX_NTT_INVERSE | (bit_reversed ? KZGX_NTT_BITREV : 0), e.data()),
+        "kzgx_ntt");
+  return poly(unflat(e));
+}
+
+std::vector<Fr> poly::evaluate_domain(unsigned log2n, bool bit_reversed) const {
+  if ((int)log2n > kzgx_ntt_max_log2(g_curve))
+    throw std::invalid_argument("evaluate_domain: size exceeds the curve's power-of-two domain");
+  const size_t m = (size_t)1 << log2n;
+  if (data.size() > m) throw std::invalid_argument("evaluate_domain: the polynomial has more coefficients than the domain");
+  std::vector<uint64_t> c(4 * m, 0);  // zero-padded to the domain
+  for (size_t i = 0; i < data.size(); i++) std::memcpy(&c[4 * i], data[i].v.data(), 32);
+  check(kzgx_ntt(default_ctx(), c.data(), log2n, 1, bit_reversed ? KZGX_NTT_BITREV : 0, c.data()), "kzgx_ntt");
+  return unflat(c);
+}
+
 // serialize_ZZ_pX (util.cpp:118-140): i64 degree, then per coefficient a u8
 // byte count and the minimal little-endian bytes
 std::vector<uint8_t> poly::serialize() {
@@ -636,6 +680,44 @@ std::vector<proof> trusted_setup::create_proofs(const kzg::poly& p, const std::v
   check(kzgx_prove_single_batch(ctx, c.data(), P.size(), 0, zs.data(), points.size(), out.data(), inf.data(),
                                 nullptr),
         "kzgx_prove_single_batch");
+  for (size_t j = 0; j < points.size(); j++) res.push_back(proof(to_g1(&out[2 * nl * j], inf[j])));
+  return res;
+}
+
+std::vector<commit> trusted_setup::create_commits_from_evaluations(const std::vector<std::vector<Fr>>& evals,
+                                                                   bool bit_reversed) {
+  std::vector<commit> res;
+  if (evals.empty()) return res;
+  const size_t m = evals[0].size();
+  const unsigned k = domain_log2(m, "create_commits_from_evaluations");
+  for (auto& e : evals)
+    if (e.size() != m) throw std::invalid_argument("create_commits_from_evaluations: vectors of different sizes");
+  if (m >= n) throw std::invalid_argument("the domain must be smaller than the setup size (num_coeffs)");
+  std::vector<uint64_t> s(4 * m * evals.size());
+  for (size_t b = 0; b < evals.size(); b++) std::memcpy(&s[4 * m * b], flat(evals[b]).data(), 32 * m);
+  const int nl = base_limbs();
+  std::vector<uint64_t> out(2 * nl * evals.size());
+  std::vector<int> inf(evals.size());
+  check(kzgx_commit_evals_batch(ctx, s.data(), k, evals.size(), bit_reversed ? KZGX_NTT_BITREV : 0, out.data(),
+                                inf.data()),
+        "kzgx_commit_evals_batch");
+  for (size_t b = 0; b < evals.size(); b++) res.push_back(commit(to_g1(&out[2 * nl * b], inf[b])));
+  return res;
+}
+
+std::vector<proof> trusted_setup::create_proofs_from_evaluations(const std::vector<Fr>& evals,
+                                                                const std::vector<Fr>& points, bool bit_reversed) {
+  std::vector<proof> res;
+  const unsigned k = domain_log2(evals.size(), "create_proofs_from_evaluations");
+  if (evals.size() >= n) throw std::invalid_argument("the domain must be smaller than the setup size (num_coeffs)");
+  if (points.empty()) return res;
+  auto e = flat(evals), zs = flat(points);
+  const int nl = base_limbs();
+  std::vector<uint64_t> out(2 * nl * points.size());
+  std::vector<int> inf(points.size());
+  check(kzgx_prove_evals_batch(ctx, e.data(), k, 0, zs.data(), points.size(), bit_reversed ? KZGX_NTT_BITREV : 0,
+                               out.data(), inf.data(), nullptr),
+        "kzgx_prove_evals_batch");
   for (size_t j = 0; j < points.size(); j++) res.push_back(proof(to_g1(&out[2 * nl * j], inf[j])));
   return res;
 }

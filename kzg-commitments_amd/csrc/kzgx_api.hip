@@ -579,7 +579,7 @@ void kzgx_destroy(kzgx_ctx* ctx) {
   Ctx& c = ctx->c;
   void* bufs[] = {c.d_table, c.d_table_small, c.d_table_big, c.d_inf, c.d_stage[0], c.d_stage[1], c.d_stage[2], c.d_stage[3],
                   c.d_poly_ws, c.d_poly_ws2, ctx->d_srs_canon, ctx->d_srs2_canon, c.d_g2_ws, ctx->d_vw, ctx->d_g2tab,
-                  c.d_lift};
+                  c.d_lift, c.d_ntt_tw};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->d_chk)
@@ -589,13 +589,14 @@ void kzgx_destroy(kzgx_ctx* ctx) {
   for (auto& w : c.ws) {
     void* wb[] = {w.counts, w.offsets, w.cursors, w.entries, w.bsum,  w.heads,
                   w.tails,  w.tailk,   w.rt,      w.q,       w.parts, w.fpart, w.fsum, w.gpart, w.gmeta, w.sstate, w.qbig,
-                  w.lat_cnt, w.var_tab, w.var_parts, w.var_scal, w.var_pt, w.var_inf};
+                  w.lat_cnt, w.var_tab, w.var_parts, w.var_scal, w.var_pt, w.var_inf, w.ntt_tmp, w.ntt_coef};
     for (void* p : wb)
       if (p) (void)hipFree(p);
     if (w.done) (void)hipEventDestroy(w.done);
   }
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (c.small_ev) (void)hipEventDestroy(c.small_ev);
+  if (c.ntt_ev) (void)hipEventDestroy(c.ntt_ev);
   if (ctx->side) {
     (void)hipStreamSynchronize(ctx->side);
     stream_give(c.device, ctx->side);
@@ -1855,6 +1856,157 @@ int kzgx_verify_aggregate_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, con
                                   const uint64_t* ys, const uint64_t* challenges, size_t count, int subgroup, int* ok) {
   return verify_aggregate_host(ctx, commits_xy, commit_inf, proofs_xy, proof_inf, zs, ys, challenges, count, true,
                                subgroup, ok);
+}
+
+// ---- evaluation form ------------------------------------------------------------
+int kzgx_ntt_max_log2(int curve) { return kzgx::ntt_max_log2(curve); }
+
+int kzgx_domain_root(int curve, unsigned log2n, uint64_t* root) {
+  if (!root) return KZGX_ERR_ARG;
+  const uint32_t* w = nullptr;
+  if (curve == KZGX_CURVE_BN254 && log2n <= (unsigned)kzgx::BN254FrNtt::TWO_ADICITY)
+    w = kzgx::BN254FrNtt::ROOT[log2n];
+  else if (curve == KZGX_CURVE_BLS12381 && log2n <= (unsigned)kzgx::BLS12381FrNtt::TWO_ADICITY)
+    w = kzgx::BLS12381FrNtt::ROOT[log2n];
+  if (!w) return KZGX_ERR_ARG;
+  for (int i = 0; i < 4; i++) root[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+  return KZGX_OK;
+}
+
+int kzgx_ntt_device(kzgx_ctx* ctx, const void* d_in, size_t in_stride, void* d_out, size_t out_stride,
+                    unsigned log2n, size_t batch, int flags, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  if ((flags & ~(KZGX_NTT_INVERSE | KZGX_NTT_BITREV)) || (int)log2n > kzgx::ntt_max_log2(ctx->c.curve))
+    return KZGX_ERR_ARG;
+  const size_t n = (size_t)1 << log2n;
+  if (!d_in || !d_out || in_stride < n || out_stride < n || (d_in == d_out && in_stride != out_stride))
+    return KZGX_ERR_ARG;
+  return kzgx::ntt(&ctx->c, (const uint32_t*)d_in, in_stride, (uint32_t*)d_out, out_stride, log2n, batch,
+                   (flags & KZGX_NTT_INVERSE) != 0, (flags & KZGX_NTT_BITREV) != 0, pick(ctx, stream));
+}
+
+int kzgx_ntt(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, size_t batch, int flags, uint64_t* out) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  if ((int)log2n > kzgx::ntt_max_log2(ctx->c.curve) || !in || !out) return KZGX_ERR_ARG;
+  const size_t n = (size_t)1 << log2n, bytes = batch * n * 32;
+  void* d = nullptr;
+  KZGX_TRY(stage(ctx, 0, bytes, &d));
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d, in, bytes, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx_ntt_device(ctx, d, n, d, n, log2n, batch, flags, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  return KZGX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the argument checks the commit and the prove entries share; *n = 2^log2n
+int evals_args(kzgx_ctx* ctx, unsigned log2n, size_t eval_stride, bool stride0_ok, int flags, size_t* n) {
+  if ((flags & ~KZGX_NTT_BITREV) || (int)log2n > kzgx::ntt_max_log2(ctx->c.curve)) return KZGX_ERR_ARG;
+  *n = (size_t)1 << log2n;
+  if (eval_stride < *n && !(stride0_ok && eval_stride == 0)) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  if (*n > ctx->c.n_srs) return KZGX_ERR_DEGREE;
+  return KZGX_OK;
+}
+
+// inverse NTT of npolys evaluation vectors into the stream's coefficient
+// workspace (n scalars apart); the caller's buffer is only read
+int evals_to_coeffs(kzgx_ctx* ctx, const kzgx::WsLease& ws, const void* d_evals, size_t eval_stride, unsigned log2n,
+                    size_t npolys, int flags, hipStream_t st) {
+  const size_t n = (size_t)1 << log2n;
+  KZGX_TRY(kzgx::dev_alloc(&ctx->c, (void**)&ws->ntt_coef, npolys * n * 32, &ws->ntt_coef_b));
+  return kzgx::ntt(&ctx->c, (const uint32_t*)d_evals, eval_stride ? eval_stride : n, ws->ntt_coef, n, log2n, npolys,
+                   true, (flags & KZGX_NTT_BITREV) != 0, st);
+}
+}  // namespace
+
+extern "C" {
+
+int kzgx_commit_evals_batch_device(kzgx_ctx* ctx, const void* d_evals, unsigned log2n, size_t batch,
+                                   size_t eval_stride, int flags, void* d_out_xy, void* d_out_is_inf,
+                                   void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  size_t n = 0;
+  KZGX_TRY(evals_args(ctx, log2n, eval_stride, false, flags, &n));
+  if (!d_evals || !d_out_xy || !d_out_is_inf || batch > 65535) return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  KZGX_TRY(evals_to_coeffs(ctx, ws, d_evals, eval_stride, log2n, batch, flags, st));
+  return kzgx_msm_g1_batch_device(ctx, ws->ntt_coef, n, batch, n, d_out_xy, d_out_is_inf, st);
+}
+
+int kzgx_commit_evals_batch(kzgx_ctx* ctx, const uint64_t* evals, unsigned log2n, size_t batch, int flags,
+                            uint64_t* out_xy, int* out_is_inf) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  size_t n = 0;
+  KZGX_TRY(evals_args(ctx, log2n, (size_t)-1, false, flags, &n));  // rows are packed: no stride to check
+  if (!evals || !out_xy || !out_is_inf) return KZGX_ERR_ARG;
+  const size_t eb = batch * n * 32, ob = batch * point_words(ctx) * 4;
+  void *d_e, *d_o;
+  KZGX_TRY(stage(ctx, 0, eb, &d_e));
+  KZGX_TRY(stage(ctx, 1, align256(ob) + batch * 4, &d_o));
+  void* d_i = (char*)d_o + align256(ob);
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_e, evals, eb, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx_commit_evals_batch_device(ctx, d_e, log2n, batch, n, flags, d_o, d_i, st));
+  std::vector<uint32_t> inf(batch);
+  KZGX_TRY_HIP(hipMemcpyAsync(out_xy, d_o, ob, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(inf.data(), d_i, batch * 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t b = 0; b < batch; b++) out_is_inf[b] = (int)inf[b];
+  return KZGX_OK;
+}
+
+int kzgx_prove_evals_batch_device(kzgx_ctx* ctx, const void* d_evals, unsigned log2n, size_t eval_stride,
+                                  const void* d_z, size_t batch, int flags, void* d_out_xy,
+                                  void* d_out_is_inf, void* d_y, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  size_t n = 0;
+  KZGX_TRY(evals_args(ctx, log2n, eval_stride, true, flags, &n));
+  if (!d_evals || !d_z || !d_out_xy || !d_out_is_inf || batch > 65535) return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  KZGX_TRY(evals_to_coeffs(ctx, ws, d_evals, eval_stride, log2n, eval_stride ? batch : 1, flags, st));
+  return kzgx_prove_single_batch_device(ctx, ws->ntt_coef, n, eval_stride ? n : 0, d_z, batch, d_out_xy,
+                                        d_out_is_inf, d_y, st);
+}
+
+int kzgx_prove_evals_batch(kzgx_ctx* ctx, const uint64_t* evals, unsigned log2n, size_t eval_stride,
+                           const uint64_t* zs, size_t batch, int flags, uint64_t* out_xy, int* out_is_inf,
+                           uint64_t* out_y) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  size_t n = 0;
+  KZGX_TRY(evals_args(ctx, log2n, eval_stride, true, flags, &n));
+  if (!evals || !zs || !out_xy || !out_is_inf) return KZGX_ERR_ARG;
+  const size_t eb = (eval_stride ? (batch - 1) * eval_stride + n : n) * 32, ob = batch * point_words(ctx) * 4;
+  const size_t i_off = align256(ob), y_off = i_off + align256(batch * 4);
+  void *d_e, *d_z, *d_o;
+  KZGX_TRY(stage(ctx, 0, eb, &d_e));
+  KZGX_TRY(stage(ctx, 1, batch * 32, &d_z));
+  KZGX_TRY(stage(ctx, 2, y_off + batch * 32, &d_o));
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_e, evals, eb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_z, zs, batch * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx_prove_evals_batch_device(ctx, d_e, log2n, eval_stride, d_z, batch, flags, d_o, (char*)d_o + i_off,
+                                         (char*)d_o + y_off, st));
+  std::vector<uint32_t> inf(batch);
+  KZGX_TRY_HIP(hipMemcpyAsync(out_xy, d_o, ob, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(inf.data(), (char*)d_o + i_off, batch * 4, hipMemcpyDeviceToHost, st));
+  if (out_y) KZGX_TRY_HIP(hipMemcpyAsync(out_y, (char*)d_o + y_off, batch * 32, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t b = 0; b < batch; b++) out_is_inf[b] = (int)inf[b];
+  return KZGX_OK;
 }
 
 }  // extern "C"

@@ -56,6 +56,10 @@ struct MsmWs {
   uint8_t* var_inf = nullptr;
   size_t var_tab_b = 0, var_parts_b = 0, var_scal_b = 0, var_pt_b = 0, var_inf_b = 0;
   uint32_t* lat_cnt = nullptr;  // [64] arrival counters of the one-launch latency path (msm_fixed.hip)
+  // evaluation form (ntt.hip, kzgx_api.hip): the two-pass transform's intermediate,
+  // and the coefficients handed on to the MSM / the opening pipeline
+  uint32_t *ntt_tmp = nullptr, *ntt_coef = nullptr;
+  size_t ntt_tmp_b = 0, ntt_coef_b = 0;
   size_t counts_b = 0, offsets_b = 0, cursors_b = 0, entries_b = 0, bsum_b = 0, heads_b = 0, tails_b = 0, tailk_b = 0,
          rt_b = 0, q_b = 0, parts_b = 0, fpart_b = 0, fsum_b = 0, gpart_b = 0, gmeta_b = 0, sstate_b = 0, qbig_b = 0;
   hipStream_t owner = nullptr;  // workspaces are per stream so calls on
@@ -88,6 +92,13 @@ class WsLease {
 };
 
 constexpr int KZGX_MAX_STREAMS = 8;
+
+// Fr NTT (ntt.hip): the largest transform, the largest one a workgroup runs
+// out of LDS (2^12 x 32 B = 128 KiB of the CU's 160 KiB), and the 32 KiB tile
+// of the small sizes
+constexpr int NTT_MAX_LOG2 = KZGX_NTT_MAX_LOG2;
+constexpr int NTT_TILE_LOG2 = KZGX_NTT_TILE_LOG2;
+constexpr int NTT_SMALL_TILE_LOG2 = 10;
 
 // precomputed odd multiples of the SRS prefix (msm_fixed.hip, indexed by
 // the regular odd digits of fixed_accum.hpp):
@@ -244,6 +255,12 @@ struct Ctx {
   size_t g2_ws_b = 0;
   uint32_t* d_lift = nullptr;  // msm_partial_xyzz's affine result before the lift
   size_t lift_b = 0;
+  // Fr NTT twiddles (ntt.hip): w^j, j <= 2^(ntt_log2 - 1), Montgomery form, for
+  // the 2^ntt_log2-th root (-1: none yet); ntt_ev is recorded behind the build
+  uint32_t* d_ntt_tw = nullptr;
+  size_t ntt_tw_b = 0;
+  int ntt_log2 = -1;
+  hipEvent_t ntt_ev = nullptr;
   // staging for host-pointer entry points
   void* d_stage[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t stage_b[4] = {0, 0, 0, 0};
@@ -337,6 +354,13 @@ int poly_interpolate(Ctx* ctx, const uint32_t* d_x, const uint32_t* d_y, size_t 
                      hipStream_t st);
 int verify_ws_reserve(Ctx* ctx, size_t n);  // poly.hip: workspaces of an n-point verify_proof
 int g2_ws_reserve(Ctx* ctx, size_t n);      // pairing.hip: an n-point G2 MSM's workspace
+
+// Fr NTT (ntt.hip): batch transforms of 2^log2n scalars, in_stride / out_stride
+// scalars apart (d_in == d_out allowed with equal strides); bitrev: the
+// evaluation side is in bit-reversed order.  Asynchronous on st.
+int ntt_max_log2(int curve);
+int ntt(Ctx* ctx, const uint32_t* d_in, size_t in_stride, uint32_t* d_out, size_t out_stride, unsigned log2n,
+        size_t batch, bool inverse, bool bitrev, hipStream_t st);
 
 // verify path: G2 SRS, polyeval_G2, pairing (pairing.hip)
 int gen_srs_g2_points(Ctx* ctx, const uint32_t* d_tau, size_t start, size_t n, uint32_t* d_out, hipStream_t st);

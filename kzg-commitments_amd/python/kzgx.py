@@ -36,7 +36,24 @@ EXPORTS = [
     "kzgx_msm_g1_points", "kzgx_msm_g1_points_device", "kzgx_verify_aggregate", "kzgx_verify_aggregate_device",
     "kzgx_g1_check_batch", "kzgx_g1_check_batch_device", "kzgx_g2_check_batch", "kzgx_srs_check",
     "kzgx_verify_aggregate_checked", "kzgx_verify_aggregate_checked_device",
+    "kzgx_ntt_max_log2", "kzgx_domain_root", "kzgx_ntt", "kzgx_ntt_device", "kzgx_commit_evals_batch",
+    "kzgx_commit_evals_batch_device", "kzgx_prove_evals_batch", "kzgx_prove_evals_batch_device",
 ]
+
+
+def _header_define(name: str) -> int:
+    """an integer #define of include/kzg_gpu.h (the one place such constants live)"""
+    import re
+    with open(os.path.join(os.path.dirname(PKG_DIR), "include", "kzg_gpu.h")) as f:
+        return int(re.search(r"^#define %s (-?\d+)\b" % name, f.read(), re.M).group(1))
+
+
+# evaluation form: flag bits, the largest transform, and the largest one a
+# workgroup runs out of LDS (above it the transform takes two passes)
+NTT_INVERSE = _header_define("KZGX_NTT_INVERSE")
+NTT_BITREV = _header_define("KZGX_NTT_BITREV")
+NTT_MAX_LOG2 = _header_define("KZGX_NTT_MAX_LOG2")
+NTT_TILE_LOG2 = _header_define("KZGX_NTT_TILE_LOG2")
 
 _lib = None
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -143,6 +160,17 @@ def lib():
                                                              ctypes.c_int, intp]),
             "kzgx_verify_aggregate_checked_device": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, sz, ctypes.c_int,
                                                                     vp, vp]),
+            "kzgx_ntt_max_log2": (ctypes.c_int, [ctypes.c_int]),
+            "kzgx_domain_root": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint, u64p]),
+            "kzgx_ntt": (ctypes.c_int, [vp, u64p, ctypes.c_uint, sz, ctypes.c_int, u64p]),
+            "kzgx_ntt_device": (ctypes.c_int, [vp, vp, sz, vp, sz, ctypes.c_uint, sz, ctypes.c_int, vp]),
+            "kzgx_commit_evals_batch": (ctypes.c_int, [vp, u64p, ctypes.c_uint, sz, ctypes.c_int, u64p, intp]),
+            "kzgx_commit_evals_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, sz, ctypes.c_int, vp, vp,
+                                                              vp]),
+            "kzgx_prove_evals_batch": (ctypes.c_int, [vp, u64p, ctypes.c_uint, sz, u64p, sz, ctypes.c_int, u64p,
+                                                      intp, u64p]),
+            "kzgx_prove_evals_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, vp, sz, ctypes.c_int, vp, vp,
+                                                             vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -202,6 +230,28 @@ def fixed_base_bytes(curve: str, c: int, n_points: int) -> int:
     b = sz(0)
     _chk(lib().kzgx_fixed_base_bytes(CURVES[curve], c, n_points, ctypes.byref(b)), "kzgx_fixed_base_bytes")
     return b.value
+
+
+def ntt_max_log2(curve: str) -> int:
+    """kzgx_ntt_max_log2: the largest log2 n of the curve's NTT (host arithmetic, no device)"""
+    return lib().kzgx_ntt_max_log2(CURVES[curve])
+
+
+def domain_root(curve: str, log2n: int) -> int:
+    """kzgx_domain_root: the generator of the size-2^log2n domain as an integer (no device)"""
+    w = np.zeros(4, dtype=np.uint64)
+    _chk(lib().kzgx_domain_root(CURVES[curve], log2n, _p(w)), "kzgx_domain_root")
+    return sum(int(w[i]) << (64 * i) for i in range(4))
+
+
+def _ntt_flags(inverse: bool = False, bitrev: bool = False) -> int:
+    return (NTT_INVERSE if inverse else 0) | (NTT_BITREV if bitrev else 0)
+
+
+def _log2_exact(n: int) -> int:
+    if n < 1 or n & (n - 1):
+        raise ValueError("size %d is not a power of two" % n)
+    return n.bit_length() - 1
 
 
 class Context:
@@ -669,3 +719,56 @@ class Context:
         _chk(lib().kzgx_verify_aggregate_checked_device(self.h, d_commits, d_commit_inf, d_proofs, d_proof_inf, d_z,
                                                         d_y, d_challenges, count, int(bool(subgroup)), d_ok, stream),
              "kzgx_verify_aggregate_checked_device")
+
+    # ---- evaluation form: Fr NTT, commits and openings from evaluations ----
+    def ntt(self, a, inverse: bool = False, bitrev: bool = False) -> np.ndarray:
+        """kzgx_ntt of one transform ((n, 4) input) or a batch ((batch, n, 4)); n a power of two.
+        bitrev: the evaluation side (forward output, inverse input) is in bit-reversed order."""
+        x = np.ascontiguousarray(a, dtype=np.uint64)
+        if x.ndim == 2:
+            x = x.reshape(1, -1, 4)
+        batch, n = x.shape[0], x.shape[1]
+        out = np.zeros_like(x)
+        _chk(lib().kzgx_ntt(self.h, _p(x), _log2_exact(n), batch, _ntt_flags(inverse, bitrev), _p(out)), "kzgx_ntt")
+        return out.reshape(np.shape(a))
+
+    def ntt_device(self, d_in, in_stride, d_out, out_stride, log2n, batch, inverse=False, bitrev=False, stream=None):
+        """kzgx_ntt_device: device pointers, strides in scalars, enqueued on stream (d_in == d_out allowed)."""
+        _chk(lib().kzgx_ntt_device(self.h, d_in, in_stride, d_out, out_stride, log2n, batch,
+                                   _ntt_flags(inverse, bitrev), stream), "kzgx_ntt_device")
+
+    def commit_evals(self, evals, bitrev: bool = False):
+        """kzgx_commit_evals_batch: evals (batch, n, 4) -> (xy, is_inf), the commits of the interpolants."""
+        e = np.ascontiguousarray(evals, dtype=np.uint64)
+        if e.ndim == 2:
+            e = e.reshape(1, -1, 4)
+        batch, n = e.shape[0], e.shape[1]
+        out = np.zeros((batch, 2 * self.w64), dtype=np.uint64)
+        inf = np.zeros(batch, dtype=np.int32)
+        _chk(lib().kzgx_commit_evals_batch(self.h, _p(e), _log2_exact(n), batch, _ntt_flags(bitrev=bitrev), _p(out),
+                                           inf.ctypes.data_as(intp)), "kzgx_commit_evals_batch")
+        return out, inf.astype(bool)
+
+    def commit_evals_device(self, d_evals, log2n, batch, stride, d_out, d_inf, bitrev=False, stream=None):
+        _chk(lib().kzgx_commit_evals_batch_device(self.h, d_evals, log2n, batch, stride, _ntt_flags(bitrev=bitrev),
+                                                  d_out, d_inf, stream), "kzgx_commit_evals_batch_device")
+
+    def prove_evals(self, evals, zs, shared: bool = True, bitrev: bool = False):
+        """kzgx_prove_evals_batch: evals (n, 4) shared (shared=True) or (batch, n, 4) -> (xy, is_inf, y)."""
+        z = as_scalars(zs)
+        batch = z.shape[0]
+        e = np.ascontiguousarray(evals, dtype=np.uint64)
+        n = e.shape[-2]
+        out = np.zeros((batch, 2 * self.w64), dtype=np.uint64)
+        inf = np.zeros(batch, dtype=np.int32)
+        y = np.zeros((batch, 4), dtype=np.uint64)
+        _chk(lib().kzgx_prove_evals_batch(self.h, _p(e), _log2_exact(n), 0 if shared else n, _p(z), batch,
+                                          _ntt_flags(bitrev=bitrev), _p(out), inf.ctypes.data_as(intp), _p(y)),
+             "kzgx_prove_evals_batch")
+        return out, inf.astype(bool), y
+
+    def prove_evals_device(self, d_evals, log2n, stride, d_z, batch, d_out, d_inf, d_y=None, bitrev=False,
+                           stream=None):
+        _chk(lib().kzgx_prove_evals_batch_device(self.h, d_evals, log2n, stride, d_z, batch,
+                                                 _ntt_flags(bitrev=bitrev), d_out, d_inf, d_y, stream),
+             "kzgx_prove_evals_batch_device")

@@ -223,6 +223,18 @@ class trusted_setup {
    *  @throws std::invalid_argument as create_commits_from_evaluations */
   std::vector<proof> create_proofs_from_evaluations(const std::vector<Fr>& evals, const std::vector<Fr>& points,
                                                     bool bit_reversed = false);
+  /** Extension: the 2^log2n single-point openings of p at every point of the
+   *  size-2^log2n domain in one GPU pass of Theta(n log n) group operations
+   *  (kzgx_prove_all_batch): element i opens at w^i, w = domain_root(log2n), or
+   *  with bit_reversed element (bit reversal of i).  Each equals
+   *  create_proofs_from_evaluations at that point.
+   *  @throws std::invalid_argument if deg + 1 > 2^log2n, the twice larger
+   *          domain exceeds the curve's (BN254: log2n > 1), or 2^log2n >= size() */
+  std::vector<proof> create_all_proofs(const poly& p, unsigned log2n, bool bit_reversed = false);
+  /** Extension: the same for the polynomial given by its values on the domain
+   *  (bit-reversed on both sides with bit_reversed).
+   *  @throws std::invalid_argument as create_commits_from_evaluations and create_all_proofs */
+  std::vector<proof> create_all_proofs_from_evaluations(const std::vector<Fr>& evals, bool bit_reversed = false);
   /** Extension: many single-point verify_proof calls in one GPU pass;
    *  result k == verify_proof(commits[k], proofs[k], blob {points[k]}). */
   std::vector<bool> verify_proofs(std::vector<commit>& commits, std::vector<proof>& proofs,

@@ -20,7 +20,9 @@
  * aggregated verification, batched point validation, and the evaluation form --
  * kzgx_ntt*, kzgx_commit_evals_batch*, kzgx_prove_evals_batch*: a radix-2 Fr NTT
  * and commits / openings of polynomials given by their values on a power-of-two
- * domain of roots of unity (BLS12-381 up to 2^22 values; BN254 only up to 4).
+ * domain of roots of unity (BLS12-381 up to 2^22 values; BN254 only up to 4);
+ * kzgx_g1_ntt*, kzgx_prove_all_*: the same transform over G1 points, and all n
+ * openings of a polynomial on its size-n domain in Theta(n log n) group operations.
  *
  * Conventions
  *   - plain pointers and sizes only; no torch / HIP types in signatures
@@ -474,6 +476,81 @@ int kzgx_prove_evals_batch(kzgx_ctx* ctx, const uint64_t* evals, unsigned log2n,
 int kzgx_prove_evals_batch_device(kzgx_ctx* ctx, const void* d_evals, unsigned log2n, size_t eval_stride,
                                   const void* d_z, size_t batch, int flags, void* d_out_xy,
                                   void* d_out_is_inf, void* d_y, void* stream);
+
+/* ---- G1 NTT (extension) ---------------------------------------------------------------
+ * The discrete Fourier transform of the evaluation form over G1 points instead
+ * of scalars, on the same domains and with the same index conventions as
+ * kzgx_ntt:  forward: out[i] = sum_j [w^(i j)] in[j];  inverse
+ * (KZGX_NTT_INVERSE): out[j] = [n^-1] sum_i [w^(-i j)] in[i].  The coefficient
+ * side is in natural order; with KZGX_NTT_BITREV the evaluation side is indexed
+ * by the bit reversal of i.  The inverse transform of an SRS prefix is the
+ * Lagrange-basis setup of that domain.  No reference counterpart.
+ *  Points are canonical affine in and out, batch x n of them, packed; all-zero
+ *   or a set flag is infinity (in_is_inf may be NULL), as in kzgx_msm_g1_points,
+ *   and like there they are taken as on the curve (not checked).  Every step is
+ *   an exact group operation (equal, opposite and infinite operands included),
+ *   so the result is bit-exact with any other correct evaluation.  No SRS is
+ *   needed.
+ *  One launch per radix-2 stage, one lane per butterfly; a twiddle costs one
+ *   255-bit scalar multiplication.  The transforms of a call run in chunks of at
+ *   most KZGX_G1_NTT_CHUNK_POINTS points (one transform at least), which bounds
+ *   the workspace at max(KZGX_G1_NTT_CHUNK_POINTS, n) XYZZ records (224 B each
+ *   on BLS12-381, 144 B on BN254).
+ *  Statuses: log2n > kzgx_ntt_max_log2(curve) or an unknown flag bit:
+ *   KZGX_ERR_ARG; batch == 0: KZGX_OK. */
+#define KZGX_G1_NTT_CHUNK_POINTS 262144
+int kzgx_g1_ntt(kzgx_ctx* ctx, const uint64_t* in_xy, const int* in_is_inf, unsigned log2n, size_t batch, int flags,
+                uint64_t* out_xy, int* out_is_inf);
+/* device pointers (flags uint32, d_in_is_inf may be NULL), asynchronous on
+ * stream (NULL = the context's); the input is only read, d_out_xy may not
+ * overlap it */
+int kzgx_g1_ntt_device(kzgx_ctx* ctx, const void* d_in_xy, const void* d_in_is_inf, void* d_out_xy,
+                       void* d_out_is_inf, unsigned log2n, size_t batch, int flags, void* stream);
+
+/* ---- all-domain openings (extension) ------------------------------------------------
+ * The n = 2^log2n single-point proofs of a polynomial of n coefficients at every
+ * point of the size-n domain at once (Feist-Khovratovich, "FK20"): proof (b, i)
+ * opens polynomial b at z = w^i, w = kzgx_domain_root(curve, log2n), and is the
+ * same group element -- the same canonical limbs -- as
+ * kzgx_prove_single_batch / kzgx_prove_evals_batch give for that z.  With
+ * KZGX_NTT_BITREV proof i sits at the bit reversal of i.  No reference
+ * counterpart.
+ *  Work: one Fr NTT of 2n scalars, 2n scalar multiplications by the cached setup
+ *   X = G1-DFT_2n(SRS[n-2], ..., SRS[0], O, ...), an inverse G1 NTT of 2n points
+ *   and a forward one of n: Theta(n log n) group operations per polynomial, where
+ *   the n separate openings cost Theta(n^2).  X is built from the installed SRS
+ *   on the first call of each log2n (or by kzgx_prove_all_prepare), on the
+ *   call's stream with other streams ordered behind it, kept by the context, and
+ *   dropped whenever the G1 SRS is replaced.
+ *  in: batch x n scalars -- coefficients, or with KZGX_PROVE_ALL_EVALS the values
+ *   on the domain (bit-reversed if KZGX_NTT_BITREV is set), taken through the
+ *   inverse NTT into workspace first.  The input is only read.  in_stride of
+ *   the device form: scalars between consecutive polynomials.
+ *  out_xy / out_is_inf: batch x n points and flags; out_y / d_y (may be NULL):
+ *   batch x n values P_b(w^i) in the same order.
+ *  Batching: a call runs in chunks of max(1, KZGX_G1_NTT_CHUNK_POINTS / 2n)
+ *   polynomials, so its workspace is bounded by max(KZGX_G1_NTT_CHUNK_POINTS, 2n)
+ *   XYZZ records plus as many scalars, per stream.
+ *  When it pays (BLS12-381, MI355X, profiles/prove_all.json, DESIGN.md
+ *   "All-domain openings and the G1 NTT"): a call costs about 140 ms whatever it
+ *   carries up to a few hundred thousand points, so one polynomial of n = 2^12
+ *   is SLOWER than kzgx_prove_evals_batch over the domain (143 against 61 ms);
+ *   the crossover is about 3 polynomials per call at n = 2^12 (32 of them: 197
+ *   against 1904 ms) and about n = 2^13 for a single polynomial (2^14: 163
+ *   against 890 ms; 2^16: 195 ms).  No path is chosen silently: this entry
+ *   always runs FK20, kzgx_prove_evals_batch always the n separate openings.
+ *  Statuses: log2n > kzgx_ntt_max_log2(curve) - 1 (the size-2n domain must
+ *   exist: BLS12-381 up to 21, BN254 up to 1), in_stride < n, an unknown flag:
+ *   KZGX_ERR_ARG; no SRS: KZGX_ERR_NO_SRS; 2^log2n larger than the installed SRS:
+ *   KZGX_ERR_DEGREE; batch == 0: KZGX_OK. */
+#define KZGX_PROVE_ALL_EVALS 4   /* input is evaluations on the domain, not coefficients */
+/* optional: builds X for log2n now (blocks until it is built) */
+int kzgx_prove_all_prepare(kzgx_ctx* ctx, unsigned log2n);
+int kzgx_prove_all_batch(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, size_t batch, int flags,
+                         uint64_t* out_xy, int* out_is_inf, uint64_t* out_y);
+/* device pointers, asynchronous on stream (NULL = the context's) */
+int kzgx_prove_all_batch_device(kzgx_ctx* ctx, const void* d_in, unsigned log2n, size_t batch, size_t in_stride,
+                                int flags, void* d_out_xy, void* d_out_is_inf, void* d_y, void* stream);
 
 #ifdef __cplusplus
 }

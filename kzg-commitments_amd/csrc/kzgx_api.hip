@@ -584,12 +584,18 @@ void kzgx_destroy(kzgx_ctx* ctx) {
     if (p) (void)hipFree(p);
   for (void* p : ctx->d_chk)
     if (p) (void)hipFree(p);
+  for (auto& f : c.fk) {
+    if (f.x) (void)hipFree(f.x);
+    if (f.inf) (void)hipFree(f.inf);
+    if (f.ev) (void)hipEventDestroy(f.ev);
+  }
   kzgx::fixed_free(&c);
   kzgx::fixed_free_table(c.fixed_def);
   for (auto& w : c.ws) {
     void* wb[] = {w.counts, w.offsets, w.cursors, w.entries, w.bsum,  w.heads,
                   w.tails,  w.tailk,   w.rt,      w.q,       w.parts, w.fpart, w.fsum, w.gpart, w.gmeta, w.sstate, w.qbig,
-                  w.lat_cnt, w.var_tab, w.var_parts, w.var_scal, w.var_pt, w.var_inf, w.ntt_tmp, w.ntt_coef};
+                  w.lat_cnt, w.var_tab, w.var_parts, w.var_scal, w.var_pt, w.var_inf, w.ntt_tmp, w.ntt_coef,
+                  w.g1n_rec, w.fk_c};
     for (void* p : wb)
       if (p) (void)hipFree(p);
     if (w.done) (void)hipEventDestroy(w.done);
@@ -818,6 +824,7 @@ size_t kzgx_srs_size(const kzgx_ctx* ctx) { return ctx ? ctx->c.n_srs : 0; }
 int kzgx_load_srs_g1(kzgx_ctx* ctx, const uint64_t* xy, size_t n) {
   KZGX_TRY(activate(ctx));
   ctx->vw_ready = false;
+  kzgx::prove_all_drop(&ctx->c);
   if (!xy || n == 0) return KZGX_ERR_ARG;
   const size_t bytes = n * point_words(ctx) * 4;
   KZGX_TRY(kzgx::dev_alloc(&ctx->c, (void**)&ctx->d_srs_canon, bytes, &ctx->srs_canon_b));
@@ -830,6 +837,7 @@ int kzgx_load_srs_g1(kzgx_ctx* ctx, const uint64_t* xy, size_t n) {
 int kzgx_gen_srs_g1(kzgx_ctx* ctx, const uint64_t* tau, size_t start, size_t n) {
   KZGX_TRY(activate(ctx));
   ctx->vw_ready = false;
+  kzgx::prove_all_drop(&ctx->c);
   if (!tau || n == 0 || n > 0x7fffffffu) return KZGX_ERR_ARG;
   const size_t bytes = n * point_words(ctx) * 4;
   KZGX_TRY(kzgx::dev_alloc(&ctx->c, (void**)&ctx->d_srs_canon, bytes, &ctx->srs_canon_b));
@@ -2006,6 +2014,141 @@ int kzgx_prove_evals_batch(kzgx_ctx* ctx, const uint64_t* evals, unsigned log2n,
   if (out_y) KZGX_TRY_HIP(hipMemcpyAsync(out_y, (char*)d_o + y_off, batch * 32, hipMemcpyDeviceToHost, st));
   KZGX_TRY_HIP(hipStreamSynchronize(st));
   for (size_t b = 0; b < batch; b++) out_is_inf[b] = (int)inf[b];
+  return KZGX_OK;
+}
+
+// ---- G1 NTT, all-domain openings ------------------------------------------------------
+int kzgx_g1_ntt_device(kzgx_ctx* ctx, const void* d_in_xy, const void* d_in_is_inf, void* d_out_xy,
+                       void* d_out_is_inf, unsigned log2n, size_t batch, int flags, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  if ((flags & ~(KZGX_NTT_INVERSE | KZGX_NTT_BITREV)) || (int)log2n > kzgx::ntt_max_log2(ctx->c.curve))
+    return KZGX_ERR_ARG;
+  if (!d_in_xy || !d_out_xy || !d_out_is_inf || d_in_xy == d_out_xy || batch > (SIZE_MAX >> 8 >> log2n))
+    return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  return kzgx::g1_ntt(&ctx->c, *ws, (const uint32_t*)d_in_xy, (const uint32_t*)d_in_is_inf, (uint32_t*)d_out_xy,
+                      (uint32_t*)d_out_is_inf, log2n, batch, (flags & KZGX_NTT_INVERSE) != 0,
+                      (flags & KZGX_NTT_BITREV) != 0, st);
+}
+
+int kzgx_g1_ntt(kzgx_ctx* ctx, const uint64_t* in_xy, const int* in_is_inf, unsigned log2n, size_t batch, int flags,
+                uint64_t* out_xy, int* out_is_inf) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  if ((flags & ~(KZGX_NTT_INVERSE | KZGX_NTT_BITREV)) || (int)log2n > kzgx::ntt_max_log2(ctx->c.curve))
+    return KZGX_ERR_ARG;
+  if (!in_xy || !out_xy || !out_is_inf || batch > (SIZE_MAX >> 8 >> log2n)) return KZGX_ERR_ARG;
+  const size_t cnt = batch << log2n, pb = cnt * point_words(ctx) * 4;
+  void *d_p, *d_f, *d_o;
+  KZGX_TRY(stage(ctx, 0, pb, &d_p));
+  KZGX_TRY(stage(ctx, 1, cnt * 4, &d_f));
+  KZGX_TRY(stage(ctx, 2, align256(pb) + cnt * 4, &d_o));
+  void* d_oi = (char*)d_o + align256(pb);
+  hipStream_t st = ctx->c.stream;
+  std::vector<uint32_t> f(cnt, 0u);
+  if (in_is_inf)
+    for (size_t i = 0; i < cnt; i++) f[i] = (uint32_t)(in_is_inf[i] != 0);
+  KZGX_TRY_HIP(hipMemcpyAsync(d_p, in_xy, pb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_f, f.data(), cnt * 4, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx_g1_ntt_device(ctx, d_p, d_f, d_o, d_oi, log2n, batch, flags, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(out_xy, d_o, pb, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(f.data(), d_oi, cnt * 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t i = 0; i < cnt; i++) out_is_inf[i] = (int)f[i];
+  return KZGX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the argument checks of the all-domain entries; *n = 2^log2n
+int prove_all_args(kzgx_ctx* ctx, unsigned log2n, size_t in_stride, int flags, size_t* n) {
+  if ((flags & ~(KZGX_NTT_BITREV | KZGX_PROVE_ALL_EVALS)) || (int)log2n + 1 > kzgx::ntt_max_log2(ctx->c.curve))
+    return KZGX_ERR_ARG;
+  *n = (size_t)1 << log2n;
+  if (in_stride < *n) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  if (*n > ctx->c.n_srs) return KZGX_ERR_DEGREE;
+  return KZGX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kzgx_prove_all_prepare(kzgx_ctx* ctx, unsigned log2n) {
+  KZGX_TRY(activate(ctx));
+  size_t n = 0;
+  KZGX_TRY(prove_all_args(ctx, log2n, (size_t)-1, 0, &n));
+  hipStream_t st = ctx->c.stream;
+  {
+    kzgx::WsLease ws = ctx->c.ws_for(st);
+    if (!ws) return KZGX_ERR_ARG;
+    KZGX_TRY(kzgx::prove_all_setup(&ctx->c, *ws, ctx->d_srs_canon, log2n, st));
+  }
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  return KZGX_OK;
+}
+
+int kzgx_prove_all_batch_device(kzgx_ctx* ctx, const void* d_in, unsigned log2n, size_t batch, size_t in_stride,
+                                int flags, void* d_out_xy, void* d_out_is_inf, void* d_y, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  size_t n = 0;
+  KZGX_TRY(prove_all_args(ctx, log2n, in_stride, flags, &n));
+  if (!d_in || !d_out_xy || !d_out_is_inf || batch > 0xffffffffu || batch > (SIZE_MAX >> 8 >> log2n))
+    return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const bool bitrev = (flags & KZGX_NTT_BITREV) != 0, evals = (flags & KZGX_PROVE_ALL_EVALS) != 0;
+  // chunks of polynomials, so that every workspace of the call is bounded
+  const size_t chunk = std::max<size_t>(1, kzgx::G1_NTT_CHUNK_RECORDS >> (log2n + 1)), pw = point_words(ctx);
+  for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+    const size_t cb = std::min(chunk, batch - b0);
+    const uint32_t* d_coef = (const uint32_t*)d_in + b0 * in_stride * 8;
+    uint32_t* d_yc = d_y ? (uint32_t*)d_y + b0 * n * 8 : nullptr;
+    size_t stride = in_stride;
+    if (evals) {
+      // the values are the y of every opening as they stand; the coefficients go to workspace
+      if (d_yc)
+        KZGX_TRY_HIP(hipMemcpy2DAsync(d_yc, n * 32, d_coef, in_stride * 32, n * 32, cb, hipMemcpyDeviceToDevice, st));
+      KZGX_TRY(evals_to_coeffs(ctx, ws, d_coef, in_stride, log2n, cb, flags & KZGX_NTT_BITREV, st));
+      d_coef = ws->ntt_coef;
+      stride = n;
+    } else if (d_yc) {
+      KZGX_TRY(kzgx::ntt(&ctx->c, d_coef, stride, d_yc, n, log2n, cb, false, bitrev, st));
+    }
+    KZGX_TRY(kzgx::prove_all(&ctx->c, *ws, ctx->d_srs_canon, d_coef, stride, log2n, cb, bitrev,
+                             (uint32_t*)d_out_xy + b0 * n * pw, (uint32_t*)d_out_is_inf + b0 * n, st));
+  }
+  return KZGX_OK;
+}
+
+int kzgx_prove_all_batch(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, size_t batch, int flags,
+                         uint64_t* out_xy, int* out_is_inf, uint64_t* out_y) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  size_t n = 0;
+  KZGX_TRY(prove_all_args(ctx, log2n, (size_t)-1, flags, &n));  // rows are packed: no stride to check
+  if (!in || !out_xy || !out_is_inf || batch > (SIZE_MAX >> 8 >> log2n)) return KZGX_ERR_ARG;
+  const size_t cnt = batch * n, sb = cnt * 32, ob = cnt * point_words(ctx) * 4;
+  const size_t i_off = align256(ob), y_off = i_off + align256(cnt * 4);
+  void *d_e, *d_o;
+  KZGX_TRY(stage(ctx, 0, sb, &d_e));
+  KZGX_TRY(stage(ctx, 1, y_off + sb, &d_o));
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_e, in, sb, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx_prove_all_batch_device(ctx, d_e, log2n, batch, n, flags, d_o, (char*)d_o + i_off,
+                                       out_y ? (char*)d_o + y_off : nullptr, st));
+  std::vector<uint32_t> inf(cnt);
+  KZGX_TRY_HIP(hipMemcpyAsync(out_xy, d_o, ob, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(inf.data(), (char*)d_o + i_off, cnt * 4, hipMemcpyDeviceToHost, st));
+  if (out_y) KZGX_TRY_HIP(hipMemcpyAsync(out_y, (char*)d_o + y_off, sb, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t i = 0; i < cnt; i++) out_is_inf[i] = (int)inf[i];
   return KZGX_OK;
 }
 

@@ -60,6 +60,10 @@ struct MsmWs {
   // and the coefficients handed on to the MSM / the opening pipeline
   uint32_t *ntt_tmp = nullptr, *ntt_coef = nullptr;
   size_t ntt_tmp_b = 0, ntt_coef_b = 0;
+  // G1 NTT and all-domain openings (g1_ntt.hip): the XYZZ records of a chunk of
+  // transforms, and the chunk's extended coefficient vectors / their transforms
+  uint32_t *g1n_rec = nullptr, *fk_c = nullptr;
+  size_t g1n_rec_b = 0, fk_c_b = 0;
   size_t counts_b = 0, offsets_b = 0, cursors_b = 0, entries_b = 0, bsum_b = 0, heads_b = 0, tails_b = 0, tailk_b = 0,
          rt_b = 0, q_b = 0, parts_b = 0, fpart_b = 0, fsum_b = 0, gpart_b = 0, gmeta_b = 0, sstate_b = 0, qbig_b = 0;
   hipStream_t owner = nullptr;  // workspaces are per stream so calls on
@@ -99,6 +103,19 @@ constexpr int KZGX_MAX_STREAMS = 8;
 constexpr int NTT_MAX_LOG2 = KZGX_NTT_MAX_LOG2;
 constexpr int NTT_TILE_LOG2 = KZGX_NTT_TILE_LOG2;
 constexpr int NTT_SMALL_TILE_LOG2 = 10;
+// G1 NTT (g1_ntt.hip): a call's transforms run in chunks of at most this many
+// XYZZ records of workspace (one transform at least)
+constexpr size_t G1_NTT_CHUNK_RECORDS = KZGX_G1_NTT_CHUNK_POINTS;
+
+// all-domain openings (g1_ntt.hip): X = G1-DFT_2n of the reversed SRS prefix
+// for n = 2^k, packed affine Montgomery points with their infinity flags;
+// ev is recorded behind the build
+struct FkSetup {
+  uint32_t *x = nullptr, *inf = nullptr;
+  size_t x_b = 0, inf_b = 0;
+  bool ready = false;
+  hipEvent_t ev = nullptr;
+};
 
 // precomputed odd multiples of the SRS prefix (msm_fixed.hip, indexed by
 // the regular odd digits of fixed_accum.hpp):
@@ -261,6 +278,9 @@ struct Ctx {
   size_t ntt_tw_b = 0;
   int ntt_log2 = -1;
   hipEvent_t ntt_ev = nullptr;
+  // all-domain openings: the setup of each size n = 2^k in use, dropped
+  // (ready = false) whenever the G1 SRS is replaced
+  FkSetup fk[NTT_MAX_LOG2];
   // staging for host-pointer entry points
   void* d_stage[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t stage_b[4] = {0, 0, 0, 0};
@@ -361,6 +381,22 @@ int g2_ws_reserve(Ctx* ctx, size_t n);      // pairing.hip: an n-point G2 MSM's 
 int ntt_max_log2(int curve);
 int ntt(Ctx* ctx, const uint32_t* d_in, size_t in_stride, uint32_t* d_out, size_t out_stride, unsigned log2n,
         size_t batch, bool inverse, bool bitrev, hipStream_t st);
+// the twiddle table of at least the 2^log2n-th root is built, and st ordered
+// behind the build; then Ctx::d_ntt_tw / ntt_log2 describe it
+int ntt_twiddles(Ctx* ctx, unsigned log2n, hipStream_t st);
+
+// G1 NTT (g1_ntt.hip): batch transforms of 2^log2n canonical affine points
+// (d_in_inf: uint32 flags or null), packed; same conventions as ntt().  ws:
+// the caller's lease on st.
+int g1_ntt(Ctx* ctx, MsmWs& ws, const uint32_t* d_in_xy, const uint32_t* d_in_inf, uint32_t* d_out_xy,
+           uint32_t* d_out_inf, unsigned log2n, size_t batch, bool inverse, bool bitrev, hipStream_t st);
+// all-domain openings (FK20): the setup X of size 2^log2n from the installed
+// SRS (built once, st ordered behind the build), and the batch x n proofs of
+// polynomials given by n coefficients each, stride scalars apart
+int prove_all_setup(Ctx* ctx, MsmWs& ws, const uint32_t* d_srs_canon, unsigned log2n, hipStream_t st);
+int prove_all(Ctx* ctx, MsmWs& ws, const uint32_t* d_srs_canon, const uint32_t* d_coeffs, size_t stride,
+              unsigned log2n, size_t batch, bool bitrev, uint32_t* d_out_xy, uint32_t* d_out_inf, hipStream_t st);
+void prove_all_drop(Ctx* ctx);  // the SRS changed: every setup is stale
 
 // verify path: G2 SRS, polyeval_G2, pairing (pairing.hip)
 int gen_srs_g2_points(Ctx* ctx, const uint32_t* d_tau, size_t start, size_t n, uint32_t* d_out, hipStream_t st);

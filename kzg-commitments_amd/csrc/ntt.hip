@@ -319,6 +319,13 @@ int ntt_max_log2(int curve) {
   return -1;
 }
 
+int ntt_twiddles(Ctx* ctx, unsigned log2n, hipStream_t st) {
+  if ((int)log2n > ntt_max_log2(ctx->curve)) return KZGX_ERR_ARG;
+  const uint32_t k = std::max(log2n, 1u);  // the table holds w^0 .. w^(N/2): N >= 2
+  return ctx->curve == KZGX_CURVE_BN254 ? ntt_table_ensure<BN254Fr>(ctx, k, st)
+                                        : ntt_table_ensure<BLS12381Fr>(ctx, k, st);
+}
+
 int ntt(Ctx* ctx, const uint32_t* d_in, size_t in_stride, uint32_t* d_out, size_t out_stride, unsigned log2n,
         size_t batch, bool inverse, bool bitrev, hipStream_t st) {
   if ((int)log2n > ntt_max_log2(ctx->curve)) return KZGX_ERR_ARG;

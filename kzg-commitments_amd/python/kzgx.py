@@ -38,6 +38,8 @@ EXPORTS = [
     "kzgx_verify_aggregate_checked", "kzgx_verify_aggregate_checked_device",
     "kzgx_ntt_max_log2", "kzgx_domain_root", "kzgx_ntt", "kzgx_ntt_device", "kzgx_commit_evals_batch",
     "kzgx_commit_evals_batch_device", "kzgx_prove_evals_batch", "kzgx_prove_evals_batch_device",
+    "kzgx_g1_ntt", "kzgx_g1_ntt_device", "kzgx_prove_all_prepare", "kzgx_prove_all_batch",
+    "kzgx_prove_all_batch_device",
 ]
 
 
@@ -54,6 +56,10 @@ NTT_INVERSE = _header_define("KZGX_NTT_INVERSE")
 NTT_BITREV = _header_define("KZGX_NTT_BITREV")
 NTT_MAX_LOG2 = _header_define("KZGX_NTT_MAX_LOG2")
 NTT_TILE_LOG2 = _header_define("KZGX_NTT_TILE_LOG2")
+# G1 NTT and all-domain openings: the input-is-evaluations flag, and the points
+# per internal chunk of transforms
+PROVE_ALL_EVALS = _header_define("KZGX_PROVE_ALL_EVALS")
+G1_NTT_CHUNK_POINTS = _header_define("KZGX_G1_NTT_CHUNK_POINTS")
 
 _lib = None
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -171,6 +177,12 @@ def lib():
                                                       intp, u64p]),
             "kzgx_prove_evals_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, vp, sz, ctypes.c_int, vp, vp,
                                                              vp, vp]),
+            "kzgx_g1_ntt": (ctypes.c_int, [vp, u64p, intp, ctypes.c_uint, sz, ctypes.c_int, u64p, intp]),
+            "kzgx_g1_ntt_device": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_uint, sz, ctypes.c_int, vp]),
+            "kzgx_prove_all_prepare": (ctypes.c_int, [vp, ctypes.c_uint]),
+            "kzgx_prove_all_batch": (ctypes.c_int, [vp, u64p, ctypes.c_uint, sz, ctypes.c_int, u64p, intp, u64p]),
+            "kzgx_prove_all_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, sz, ctypes.c_int, vp, vp, vp,
+                                                           vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -772,3 +784,53 @@ class Context:
         _chk(lib().kzgx_prove_evals_batch_device(self.h, d_evals, log2n, stride, d_z, batch,
                                                  _ntt_flags(bitrev=bitrev), d_out, d_inf, d_y, stream),
              "kzgx_prove_evals_batch_device")
+
+    # ---- G1 NTT, all-domain openings ----
+    def g1_ntt(self, points, inf=None, inverse: bool = False, bitrev: bool = False):
+        """kzgx_g1_ntt of one transform ((n, 2 w64) points) or a batch ((batch, n, 2 w64)); inf: optional
+        flags of the same leading shape -> (points, is_inf) in the input's shape."""
+        x = np.ascontiguousarray(points, dtype=np.uint64)
+        shape = x.shape
+        if x.ndim == 2:
+            x = x.reshape(1, -1, 2 * self.w64)
+        batch, n = x.shape[0], x.shape[1]
+        f = None if inf is None else np.ascontiguousarray(inf, dtype=np.int32).reshape(batch, n)
+        out = np.zeros_like(x)
+        oi = np.zeros((batch, n), dtype=np.int32)
+        _chk(lib().kzgx_g1_ntt(self.h, _p(x), None if f is None else f.ctypes.data_as(intp), _log2_exact(n), batch,
+                               _ntt_flags(inverse, bitrev), _p(out), oi.ctypes.data_as(intp)), "kzgx_g1_ntt")
+        return out.reshape(shape), oi.astype(bool).reshape(shape[:-1])
+
+    def g1_ntt_device(self, d_in, d_in_inf, d_out, d_out_inf, log2n, batch, inverse=False, bitrev=False, stream=None):
+        """kzgx_g1_ntt_device: device pointers (uint32 flags, d_in_inf may be None), enqueued on stream."""
+        _chk(lib().kzgx_g1_ntt_device(self.h, d_in, d_in_inf, d_out, d_out_inf, log2n, batch,
+                                      _ntt_flags(inverse, bitrev), stream), "kzgx_g1_ntt_device")
+
+    def prove_all_prepare(self, log2n: int):
+        """kzgx_prove_all_prepare: build the all-domain setup of size 2^log2n now."""
+        _chk(lib().kzgx_prove_all_prepare(self.h, log2n), "kzgx_prove_all_prepare")
+
+    def prove_all(self, polys, evals: bool = False, bitrev: bool = False, want_y: bool = True):
+        """kzgx_prove_all_batch: (n, 4) or (batch, n, 4) coefficients (evals: values on the domain)
+        -> (xy (batch, n, 2 w64), is_inf (batch, n), y (batch, n, 4) or None); one polynomial
+        drops the batch axis."""
+        c = np.ascontiguousarray(polys, dtype=np.uint64)
+        single = c.ndim == 2
+        if single:
+            c = c.reshape(1, -1, 4)
+        batch, n = c.shape[0], c.shape[1]
+        out = np.zeros((batch, n, 2 * self.w64), dtype=np.uint64)
+        inf = np.zeros((batch, n), dtype=np.int32)
+        y = np.zeros((batch, n, 4), dtype=np.uint64) if want_y else None
+        flags = _ntt_flags(bitrev=bitrev) | (PROVE_ALL_EVALS if evals else 0)
+        _chk(lib().kzgx_prove_all_batch(self.h, _p(c), _log2_exact(n), batch, flags, _p(out),
+                                        inf.ctypes.data_as(intp), _p(y)), "kzgx_prove_all_batch")
+        inf = inf.astype(bool)
+        return (out[0], inf[0], None if y is None else y[0]) if single else (out, inf, y)
+
+    def prove_all_device(self, d_in, log2n, batch, stride, d_out, d_inf, d_y=None, evals=False, bitrev=False,
+                         stream=None):
+        """kzgx_prove_all_batch_device: device pointers, stride in scalars, enqueued on stream."""
+        flags = _ntt_flags(bitrev=bitrev) | (PROVE_ALL_EVALS if evals else 0)
+        _chk(lib().kzgx_prove_all_batch_device(self.h, d_in, log2n, batch, stride, flags, d_out, d_inf, d_y, stream),
+             "kzgx_prove_all_batch_device")

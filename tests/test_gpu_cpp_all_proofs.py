@@ -1,0 +1,27 @@
+"""GPU: the C++ facade's all-domain openings (trusted_setup::create_all_proofs /
+create_all_proofs_from_evaluations; include/kzg.h) driven by
+tests/cpp/test_all_proofs.cpp under kzg::init(BLS12-381) on a 300-point setup with
+the golden fixtures' tau, then the BN254 refusals."""
+import json
+import os
+import subprocess
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "tests", "cpp", "test_all_proofs")
+GOLD = os.path.join(ROOT, "tests", "golden")
+
+
+def test_cpp_all_proofs():
+    assert os.path.exists(BIN), "run __graft_entry__.build()"
+    with open(os.path.join(GOLD, "BLS12381.json")) as f:
+        tau = json.load(f)["tau"]
+    res = subprocess.run([BIN, tau], capture_output=True, text=True, timeout=300)
+    out = res.stdout.splitlines()
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
+    assert not [l for l in out if l.startswith("FAILED")]
+    assert len([l for l in out if l.startswith("PASSED")]) == 19
+    assert out[-1] == "ALL TESTS PASSED"

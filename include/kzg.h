@@ -235,6 +235,23 @@ class trusted_setup {
    *  (bit-reversed on both sides with bit_reversed).
    *  @throws std::invalid_argument as create_commits_from_evaluations and create_all_proofs */
   std::vector<proof> create_all_proofs_from_evaluations(const std::vector<Fr>& evals, bool bit_reversed = false);
+  /** Extension: one opening per coset (cell) of 2^log2l points in one GPU pass
+   *  (kzgx_prove_cosets_batch): the cosets of the size-2^log2n domain, or with
+   *  `extended` of the twice larger one (2^(log2n - log2l + 1) cells, the
+   *  data-availability layout).  Element i opens the points w^(i + R j),
+   *  j < 2^log2l, R the number of cosets, w = domain_root(log2 of R 2^log2l);
+   *  with bit_reversed element (bit reversal of i).  kzgx_coset_points lists a
+   *  cell's points; each proof equals the multi-point opening at them.
+   *  @throws std::invalid_argument as create_all_proofs, for log2l > log2n, or
+   *          if the size-2^(log2n - log2l + 1) or the opened domain exceeds the
+   *          curve's */
+  std::vector<proof> create_coset_proofs(const poly& p, unsigned log2n, unsigned log2l, bool extended = false,
+                                         bool bit_reversed = false);
+  /** Extension: the same for the polynomial given by its values on the
+   *  size-n domain (bit-reversed over n with bit_reversed).
+   *  @throws std::invalid_argument as create_commits_from_evaluations and create_coset_proofs */
+  std::vector<proof> create_coset_proofs_from_evaluations(const std::vector<Fr>& evals, unsigned log2l,
+                                                          bool extended = false, bool bit_reversed = false);
   /** Extension: many single-point verify_proof calls in one GPU pass;
    *  result k == verify_proof(commits[k], proofs[k], blob {points[k]}). */
   std::vector<bool> verify_proofs(std::vector<commit>& commits, std::vector<proof>& proofs,

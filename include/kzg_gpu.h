@@ -22,7 +22,9 @@
  * and commits / openings of polynomials given by their values on a power-of-two
  * domain of roots of unity (BLS12-381 up to 2^22 values; BN254 only up to 4);
  * kzgx_g1_ntt*, kzgx_prove_all_*: the same transform over G1 points, and all n
- * openings of a polynomial on its size-n domain in Theta(n log n) group operations.
+ * openings of a polynomial on its size-n domain in Theta(n log n) group operations;
+ * kzgx_prove_cosets_*, kzgx_coset_points: one opening per coset (cell) of that
+ * domain or of the twice larger one, all cosets at once.
  *
  * Conventions
  *   - plain pointers and sizes only; no torch / HIP types in signatures
@@ -551,6 +553,60 @@ int kzgx_prove_all_batch(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, size
 /* device pointers, asynchronous on stream (NULL = the context's) */
 int kzgx_prove_all_batch_device(kzgx_ctx* ctx, const void* d_in, unsigned log2n, size_t batch, size_t in_stride,
                                 int flags, void* d_out_xy, void* d_out_is_inf, void* d_y, void* stream);
+
+/* ---- coset (cell) openings (extension) -------------------------------------------------
+ * One proof per coset of l = 2^log2l points instead of one per point (the
+ * multi-point form of Feist-Khovratovich): for n = 2^log2n coefficients, m = n / l,
+ * ext = 1 with KZGX_PROVE_COSETS_EXTENDED else 0, there are R = m 2^ext cosets of
+ * the size-D domain, D = R l (n, or 2n when extended), w = kzgx_domain_root(curve,
+ * log2 D).  Coset i holds the points x(i, j) = w^(i + R j), j < l, the roots of
+ * X^l - a_i with a_i = w^(i l), and proof (b, i) = [q(tau)]G for q = P_b div
+ * (X^l - a_i): the same group element -- the same canonical limbs -- as
+ * kzgx_prove_range(P_b, xs = x(i, .)).  No reference counterpart.
+ *  Order: naturally proof i sits at index i and y[i l + j] = P(x(i, j)).  With
+ *   KZGX_NTT_BITREV proof i sits at the R-bit reversal of i and y is the
+ *   bit-reversed size-D evaluation array, whose chunk p of l consecutive values
+ *   is coset brev_R(p) with its points in bit-reversed order (brev_D(p l + q) =
+ *   brev_R(p) + R brev_l(q)): the cell layout of data-availability blobs.
+ *   kzgx_coset_points returns the l points of chunk `index` of y in y's order for
+ *   the given flags (only KZGX_NTT_BITREV and KZGX_PROVE_COSETS_EXTENDED matter),
+ *   the xs to hand to kzgx_verify_proof; host arithmetic, no device.
+ *  Work: a setup of l G1 NTTs of 2m points over the strided SRS (2n packed affine
+ *   points, built on the first call of each (log2n, log2l) or by
+ *   kzgx_prove_cosets_prepare, kept by the context, dropped with the G1 SRS), then
+ *   per polynomial l Fr NTTs of 2m scalars, 2n scalar multiplications folded l to
+ *   1 inside the wave (k_fkm_pointwise_sum: no per-term point reaches memory), an
+ *   inverse G1 NTT of 2m points and a forward one of R.  log2l = 0, ext = 0 gives
+ *   kzgx_prove_all_batch's output.  m = 1: every quotient is zero, every proof
+ *   infinity.
+ *  in: batch x n scalars -- coefficients, or with KZGX_PROVE_ALL_EVALS the values
+ *   on the size-n domain (bit-reversed over n if KZGX_NTT_BITREV), as in
+ *   kzgx_prove_all_batch.  The input is only read.
+ *  out_xy / out_is_inf: batch x R points and flags; out_y / d_y (may be NULL):
+ *   batch x D values.
+ *  Batching: chunks of max(1, KZGX_G1_NTT_CHUNK_POINTS / 2n) polynomials; per
+ *   polynomial the workspace is 2m XYZZ records, 2n scalars, and D scalars for y.
+ *  When it pays (BLS12-381, MI355X, profiles/prove_cosets.json, DESIGN.md "Coset
+ *   openings (multi-point FK20)"): a (12, 6) extended call is a chain of 15
+ *   latency-bound launches, about 73 ms per chunk of up to 32 polynomials, against
+ *   0.79 ms per kzgx_prove_range call (host wall clock): 1 polynomial 73.4 against
+ *   101.9 ms, 8: 75.3 against 811 ms, 64: 158.1 against 6488 ms.  A call that
+ *   carries fewer than about 90 cosets in all is SLOWER than the separate calls;
+ *   with log2l = 0 the time is kzgx_prove_all_batch's.  No path is chosen silently.
+ *  Statuses: log2l > log2n, log2n - log2l + 1 or log2n + ext larger than
+ *   kzgx_ntt_max_log2(curve), in_stride < n, an unknown flag, a NULL pointer:
+ *   KZGX_ERR_ARG; no SRS: KZGX_ERR_NO_SRS; 2^log2n larger than the installed SRS:
+ *   KZGX_ERR_DEGREE; batch == 0: KZGX_OK. */
+#define KZGX_PROVE_COSETS_EXTENDED 8 /* cosets of the size-2n domain (R = 2 n / l) */
+int kzgx_coset_points(int curve, unsigned log2n, unsigned log2l, int flags, size_t index, uint64_t* xs);
+/* optional: builds the setup of (log2n, log2l) now (blocks until it is built) */
+int kzgx_prove_cosets_prepare(kzgx_ctx* ctx, unsigned log2n, unsigned log2l);
+int kzgx_prove_cosets_batch(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, unsigned log2l, size_t batch,
+                            int flags, uint64_t* out_xy, int* out_is_inf, uint64_t* out_y);
+/* device pointers, asynchronous on stream (NULL = the context's) */
+int kzgx_prove_cosets_batch_device(kzgx_ctx* ctx, const void* d_in, unsigned log2n, unsigned log2l, size_t batch,
+                                   size_t in_stride, int flags, void* d_out_xy, void* d_out_is_inf, void* d_y,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -47,18 +47,6 @@ template <class C, int CB>
 int fixed_msm_win(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n, size_t batch, size_t stride_words,
                   uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st, uint32_t* xyzz_out);
 
-#ifdef KZGX_FIXED_INST
-// --------------------------------------------------------------------------
-// latency path (a few MSMs of <= 2^14 points): every step below runs on
-// mostly idle CUs, so the time of one call is the longest dependent chain of
-// point additions, each ~5 us (mixed) / ~8 us (XYZZ) in one lane
-// (scripts/lat_micro.py).  The chain is cut to
-//   WG mixed additions (a thread owns one point and WG of its W windows)
-//   + 6 shuffle additions (wavefront fold inside the accumulation kernel)
-//   + Q / 64 - 1 + log2(min(Q, 64)) additions (one wavefront per MSM over the
-//     Q <= 256 wavefront partials, which then converts to affine in lane 0)
-// instead of W mixed additions + two 64:1 fold levels + a separate finish.
-// --------------------------------------------------------------------------
 // lane l and lane l ^ off both add the pair, the lower lane's value first:
 // the same operands in the same order give bit-identical XYZZ values in both
 // lanes (the addition is not symmetric in representation: swapping the
@@ -87,6 +75,18 @@ KZGX_DEV Xyzz<C> xyzz_shfl_xor_add(const Xyzz<C>& acc, int off) {
   return xyzz_add_impl<C>(a, b);
 }
 
+#ifdef KZGX_FIXED_INST
+// --------------------------------------------------------------------------
+// latency path (a few MSMs of <= 2^14 points): every step below runs on
+// mostly idle CUs, so the time of one call is the longest dependent chain of
+// point additions, each ~5 us (mixed) / ~8 us (XYZZ) in one lane
+// (scripts/lat_micro.py).  The chain is cut to
+//   WG mixed additions (a thread owns one point and WG of its W windows)
+//   + 6 shuffle additions (wavefront fold inside the accumulation kernel)
+//   + Q / 64 - 1 + log2(min(Q, 64)) additions (one wavefront per MSM over the
+//     Q <= 256 wavefront partials, which then converts to affine in lane 0)
+// instead of W mixed additions + two 64:1 fold levels + a separate finish.
+// --------------------------------------------------------------------------
 // ---- the last four fold levels as cooperative additions ------------------
 // A lone wave pays for every instruction it issues whatever the number of
 // lanes doing useful work, so the last levels of a shuffle tree (8, 4, 2, 1

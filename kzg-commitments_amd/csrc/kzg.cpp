@@ -753,6 +753,47 @@ std::vector<proof> trusted_setup::create_all_proofs_from_evaluations(const std::
   return all_proofs(ctx, n, flat(evals), k, KZGX_PROVE_ALL_EVALS | (bit_reversed ? KZGX_NTT_BITREV : 0));
 }
 
+// the coset openings of one polynomial: in = 2^k scalars, coefficients or values
+static std::vector<proof> coset_proofs(kzgx_ctx* ctx, size_t n, const std::vector<uint64_t>& in, unsigned k,
+                                       unsigned kl, int flags) {
+  const int mx = kzgx_ntt_max_log2(g_curve), ext = (flags & KZGX_PROVE_COSETS_EXTENDED) ? 1 : 0;
+  if (kl > k) throw std::invalid_argument("coset proofs: a coset larger than the domain");
+  if ((int)(k - kl) + 1 > mx || (int)k + ext > mx)
+    throw std::invalid_argument("coset proofs: a domain the shape needs exceeds the curve's power-of-two domain");
+  const size_t m = (size_t)1 << k, R = (size_t)1 << (k - kl + ext);
+  if (m >= n) throw std::invalid_argument("the domain must be smaller than the setup size (num_coeffs)");
+  const int nl = base_limbs();
+  std::vector<uint64_t> out(2 * nl * R);
+  std::vector<int> inf(R);
+  check(kzgx_prove_cosets_batch(ctx, in.data(), k, kl, 1, flags, out.data(), inf.data(), nullptr),
+        "kzgx_prove_cosets_batch");
+  std::vector<proof> res;
+  for (size_t j = 0; j < R; j++) res.push_back(proof(to_g1(&out[2 * nl * j], inf[j])));
+  return res;
+}
+
+std::vector<proof> trusted_setup::create_coset_proofs(const kzg::poly& p, unsigned log2n, unsigned log2l, bool extended,
+                                                      bool bit_reversed) {
+  if ((int)log2n > kzgx_ntt_max_log2(g_curve))
+    throw std::invalid_argument("create_coset_proofs: size exceeds the curve's power-of-two domain");
+  const auto& P = p.get_poly();
+  const size_t m = (size_t)1 << log2n;
+  if (P.size() > m)
+    throw std::invalid_argument("create_coset_proofs: the polynomial has more coefficients than the domain");
+  std::vector<uint64_t> c(4 * m, 0);  // zero-padded to the domain
+  for (size_t i = 0; i < P.size(); i++) std::memcpy(&c[4 * i], P[i].v.data(), 32);
+  return coset_proofs(ctx, n, c, log2n, log2l,
+                      (extended ? KZGX_PROVE_COSETS_EXTENDED : 0) | (bit_reversed ? KZGX_NTT_BITREV : 0));
+}
+
+std::vector<proof> trusted_setup::create_coset_proofs_from_evaluations(const std::vector<Fr>& evals, unsigned log2l,
+                                                                      bool extended, bool bit_reversed) {
+  const unsigned k = domain_log2(evals.size(), "create_coset_proofs_from_evaluations");
+  return coset_proofs(ctx, n, flat(evals), k, log2l,
+                      KZGX_PROVE_ALL_EVALS | (extended ? KZGX_PROVE_COSETS_EXTENDED : 0) |
+                          (bit_reversed ? KZGX_NTT_BITREV : 0));
+}
+
 std::vector<bool> trusted_setup::verify_proofs(std::vector<commit>& commits, std::vector<proof>& proofs,
                                               const std::vector<std::pair<Fr, Fr>>& points) {
   const size_t m = commits.size();

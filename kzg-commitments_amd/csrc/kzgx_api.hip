@@ -589,13 +589,19 @@ void kzgx_destroy(kzgx_ctx* ctx) {
     if (f.inf) (void)hipFree(f.inf);
     if (f.ev) (void)hipEventDestroy(f.ev);
   }
+  for (auto& row : c.fkm)
+    for (auto& f : row) {
+      if (f.x) (void)hipFree(f.x);
+      if (f.inf) (void)hipFree(f.inf);
+      if (f.ev) (void)hipEventDestroy(f.ev);
+    }
   kzgx::fixed_free(&c);
   kzgx::fixed_free_table(c.fixed_def);
   for (auto& w : c.ws) {
     void* wb[] = {w.counts, w.offsets, w.cursors, w.entries, w.bsum,  w.heads,
                   w.tails,  w.tailk,   w.rt,      w.q,       w.parts, w.fpart, w.fsum, w.gpart, w.gmeta, w.sstate, w.qbig,
                   w.lat_cnt, w.var_tab, w.var_parts, w.var_scal, w.var_pt, w.var_inf, w.ntt_tmp, w.ntt_coef,
-                  w.g1n_rec, w.fk_c};
+                  w.g1n_rec, w.fk_c, w.fkm_y};
     for (void* p : wb)
       if (p) (void)hipFree(p);
     if (w.done) (void)hipEventDestroy(w.done);
@@ -2147,6 +2153,183 @@ int kzgx_prove_all_batch(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, size
   KZGX_TRY_HIP(hipMemcpyAsync(out_xy, d_o, ob, hipMemcpyDeviceToHost, st));
   KZGX_TRY_HIP(hipMemcpyAsync(inf.data(), (char*)d_o + i_off, cnt * 4, hipMemcpyDeviceToHost, st));
   if (out_y) KZGX_TRY_HIP(hipMemcpyAsync(out_y, (char*)d_o + y_off, sb, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t i = 0; i < cnt; i++) out_is_inf[i] = (int)inf[i];
+  return KZGX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// host Montgomery product over Fr, 8 x 32-bit limbs: out = a b 2^-256 mod r (out may alias a or b)
+template <class FR>
+void fr_host_mmul(const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  uint32_t t[10] = {0};
+  for (int i = 0; i < 8; i++) {
+    uint64_t c = 0, s;
+    for (int j = 0; j < 8; j++) {
+      s = (uint64_t)a[j] * b[i] + t[j] + c;
+      t[j] = (uint32_t)s;
+      c = s >> 32;
+    }
+    s = (uint64_t)t[8] + c;
+    t[8] = (uint32_t)s;
+    t[9] = (uint32_t)(s >> 32);
+    const uint32_t q = t[0] * FR::INV;
+    c = ((uint64_t)q * FR::P[0] + t[0]) >> 32;
+    for (int j = 1; j < 8; j++) {
+      s = (uint64_t)q * FR::P[j] + t[j] + c;
+      t[j - 1] = (uint32_t)s;
+      c = s >> 32;
+    }
+    s = (uint64_t)t[8] + c;
+    t[7] = (uint32_t)s;
+    t[8] = t[9] + (uint32_t)(s >> 32);
+  }
+  bool ge = t[8] != 0;  // t < 2 r
+  if (!ge) {
+    int i = 7;
+    while (i >= 0 && t[i] == FR::P[i]) i--;
+    ge = i < 0 || t[i] > FR::P[i];
+  }
+  uint64_t borrow = 0;
+  for (int i = 0; i < 8; i++) {
+    const uint64_t d = (uint64_t)t[i] - (ge ? FR::P[i] : 0u) - borrow;
+    out[i] = (uint32_t)d;
+    borrow = (d >> 32) & 1;
+  }
+}
+
+// xs[q] = the point of offset q in chunk `index` of y: w_D^(i + R j), with bitrev i = brev_R(index), j = brev_l(q)
+template <class FR, class T>
+void coset_points_host(unsigned kr, unsigned kl, bool bitrev, size_t index, uint64_t* xs) {
+  const auto brev = [](size_t v, unsigned bits) {
+    size_t r = 0;
+    for (unsigned b = 0; b < bits; b++) r |= ((v >> b) & 1) << (bits - 1 - b);
+    return r;
+  };
+  const size_t i = bitrev ? brev(index, kr) : index;
+  uint32_t x[8], sq[8], step[8];
+  const uint32_t one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+  fr_host_mmul<FR>(T::ROOT[kr + kl], FR::R2, sq);  // Montgomery form of w_D
+  std::copy(FR::ONE, FR::ONE + 8, x);
+  for (unsigned b = 0; b < kr; b++) {  // x = w_D^i; sq ends as w_D^R, of order l
+    if ((i >> b) & 1) fr_host_mmul<FR>(x, sq, x);
+    fr_host_mmul<FR>(sq, sq, sq);
+  }
+  std::copy(sq, sq + 8, step);
+  for (size_t j = 0; j < ((size_t)1 << kl); j++) {
+    uint32_t c[8];
+    fr_host_mmul<FR>(x, one, c);
+    uint64_t* o = xs + 4 * (bitrev ? brev(j, kl) : j);
+    for (int w = 0; w < 4; w++) o[w] = (uint64_t)c[2 * w] | ((uint64_t)c[2 * w + 1] << 32);
+    fr_host_mmul<FR>(x, step, x);
+  }
+}
+
+// the shapes of the coset entries: the size-2m and the size-D domains must exist
+bool cosets_shape_ok(int curve, unsigned log2n, unsigned log2l, int flags) {
+  const int mx = kzgx::ntt_max_log2(curve);
+  if (mx < 0 || log2n > 31 || log2l > log2n) return false;
+  if (flags & ~(KZGX_NTT_BITREV | KZGX_PROVE_ALL_EVALS | KZGX_PROVE_COSETS_EXTENDED)) return false;
+  const int ext = (flags & KZGX_PROVE_COSETS_EXTENDED) ? 1 : 0;
+  return (int)(log2n - log2l) + 1 <= mx && (int)log2n + ext <= mx;
+}
+
+// the argument checks of the coset entries; *n = 2^log2n
+int prove_cosets_args(kzgx_ctx* ctx, unsigned log2n, unsigned log2l, size_t in_stride, int flags, size_t* n) {
+  if (!cosets_shape_ok(ctx->c.curve, log2n, log2l, flags)) return KZGX_ERR_ARG;
+  *n = (size_t)1 << log2n;
+  if (in_stride < *n) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  if (*n > ctx->c.n_srs) return KZGX_ERR_DEGREE;
+  return KZGX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// ---- coset openings -------------------------------------------------------------------------
+int kzgx_coset_points(int curve, unsigned log2n, unsigned log2l, int flags, size_t index, uint64_t* xs) {
+  if (!xs || !cosets_shape_ok(curve, log2n, log2l, flags)) return KZGX_ERR_ARG;
+  const unsigned kr = log2n - log2l + ((flags & KZGX_PROVE_COSETS_EXTENDED) ? 1 : 0);
+  if (index >> kr) return KZGX_ERR_ARG;
+  const bool bitrev = (flags & KZGX_NTT_BITREV) != 0;
+  if (curve == KZGX_CURVE_BN254)
+    coset_points_host<kzgx::BN254Fr, kzgx::BN254FrNtt>(kr, log2l, bitrev, index, xs);
+  else
+    coset_points_host<kzgx::BLS12381Fr, kzgx::BLS12381FrNtt>(kr, log2l, bitrev, index, xs);
+  return KZGX_OK;
+}
+
+int kzgx_prove_cosets_prepare(kzgx_ctx* ctx, unsigned log2n, unsigned log2l) {
+  KZGX_TRY(activate(ctx));
+  size_t n = 0;
+  KZGX_TRY(prove_cosets_args(ctx, log2n, log2l, (size_t)-1, 0, &n));
+  hipStream_t st = ctx->c.stream;
+  {
+    kzgx::WsLease ws = ctx->c.ws_for(st);
+    if (!ws) return KZGX_ERR_ARG;
+    KZGX_TRY(kzgx::prove_cosets_setup(&ctx->c, *ws, ctx->d_srs_canon, log2n, log2l, st));
+  }
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  return KZGX_OK;
+}
+
+int kzgx_prove_cosets_batch_device(kzgx_ctx* ctx, const void* d_in, unsigned log2n, unsigned log2l, size_t batch,
+                                   size_t in_stride, int flags, void* d_out_xy, void* d_out_is_inf, void* d_y,
+                                   void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  size_t n = 0;
+  KZGX_TRY(prove_cosets_args(ctx, log2n, log2l, in_stride, flags, &n));
+  if (!d_in || !d_out_xy || !d_out_is_inf || batch > 0xffffffffu || batch > (SIZE_MAX >> 9 >> log2n))
+    return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const bool bitrev = (flags & KZGX_NTT_BITREV) != 0, evals = (flags & KZGX_PROVE_ALL_EVALS) != 0,
+             ext = (flags & KZGX_PROVE_COSETS_EXTENDED) != 0;
+  const size_t R = (size_t)1 << (log2n - log2l + (ext ? 1 : 0)), D = R << log2l;
+  // chunks of polynomials, so that every workspace of the call is bounded
+  const size_t chunk = std::max<size_t>(1, kzgx::G1_NTT_CHUNK_RECORDS >> (log2n + 1)), pw = point_words(ctx);
+  for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+    const size_t cb = std::min(chunk, batch - b0);
+    const uint32_t* d_coef = (const uint32_t*)d_in + b0 * in_stride * 8;
+    size_t stride = in_stride;
+    if (evals) {
+      KZGX_TRY(evals_to_coeffs(ctx, ws, d_coef, in_stride, log2n, cb, flags & KZGX_NTT_BITREV, st));
+      d_coef = ws->ntt_coef;
+      stride = n;
+    }
+    KZGX_TRY(kzgx::prove_cosets(&ctx->c, *ws, ctx->d_srs_canon, d_coef, stride, log2n, log2l, cb, ext, bitrev,
+                                (uint32_t*)d_out_xy + b0 * R * pw, (uint32_t*)d_out_is_inf + b0 * R,
+                                d_y ? (uint32_t*)d_y + b0 * D * 8 : nullptr, st));
+  }
+  return KZGX_OK;
+}
+
+int kzgx_prove_cosets_batch(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, unsigned log2l, size_t batch,
+                            int flags, uint64_t* out_xy, int* out_is_inf, uint64_t* out_y) {
+  KZGX_TRY(activate(ctx));
+  if (batch == 0) return KZGX_OK;
+  size_t n = 0;
+  KZGX_TRY(prove_cosets_args(ctx, log2n, log2l, (size_t)-1, flags, &n));  // rows are packed: no stride to check
+  if (!in || !out_xy || !out_is_inf || batch > (SIZE_MAX >> 9 >> log2n)) return KZGX_ERR_ARG;
+  const size_t R = (size_t)1 << (log2n - log2l + ((flags & KZGX_PROVE_COSETS_EXTENDED) ? 1 : 0));
+  const size_t cnt = batch * R, sb = batch * n * 32, yb = (cnt << log2l) * 32, ob = cnt * point_words(ctx) * 4;
+  const size_t i_off = align256(ob), y_off = i_off + align256(cnt * 4);
+  void *d_e, *d_o;
+  KZGX_TRY(stage(ctx, 0, sb, &d_e));
+  KZGX_TRY(stage(ctx, 1, y_off + yb, &d_o));
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_e, in, sb, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx_prove_cosets_batch_device(ctx, d_e, log2n, log2l, batch, n, flags, d_o, (char*)d_o + i_off,
+                                          out_y ? (char*)d_o + y_off : nullptr, st));
+  std::vector<uint32_t> inf(cnt);
+  KZGX_TRY_HIP(hipMemcpyAsync(out_xy, d_o, ob, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(inf.data(), (char*)d_o + i_off, cnt * 4, hipMemcpyDeviceToHost, st));
+  if (out_y) KZGX_TRY_HIP(hipMemcpyAsync(out_y, (char*)d_o + y_off, yb, hipMemcpyDeviceToHost, st));
   KZGX_TRY_HIP(hipStreamSynchronize(st));
   for (size_t i = 0; i < cnt; i++) out_is_inf[i] = (int)inf[i];
   return KZGX_OK;

@@ -64,6 +64,9 @@ struct MsmWs {
   // transforms, and the chunk's extended coefficient vectors / their transforms
   uint32_t *g1n_rec = nullptr, *fk_c = nullptr;
   size_t g1n_rec_b = 0, fk_c_b = 0;
+  // coset openings (g1_ntt.hip): a chunk's zero-padded coefficients / natural-order values for y
+  uint32_t* fkm_y = nullptr;
+  size_t fkm_y_b = 0;
   size_t counts_b = 0, offsets_b = 0, cursors_b = 0, entries_b = 0, bsum_b = 0, heads_b = 0, tails_b = 0, tailk_b = 0,
          rt_b = 0, q_b = 0, parts_b = 0, fpart_b = 0, fsum_b = 0, gpart_b = 0, gmeta_b = 0, sstate_b = 0, qbig_b = 0;
   hipStream_t owner = nullptr;  // workspaces are per stream so calls on
@@ -281,6 +284,9 @@ struct Ctx {
   // all-domain openings: the setup of each size n = 2^k in use, dropped
   // (ready = false) whenever the G1 SRS is replaced
   FkSetup fk[NTT_MAX_LOG2];
+  // coset openings: the setup of each (log2n, log2l) in use -- x[i][t] = value i
+  // of G1-DFT_2m of the stride-l SRS slice t, 2n points -- dropped with fk
+  FkSetup fkm[NTT_MAX_LOG2 + 1][NTT_MAX_LOG2 + 1];
   // staging for host-pointer entry points
   void* d_stage[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t stage_b[4] = {0, 0, 0, 0};
@@ -397,6 +403,15 @@ int prove_all_setup(Ctx* ctx, MsmWs& ws, const uint32_t* d_srs_canon, unsigned l
 int prove_all(Ctx* ctx, MsmWs& ws, const uint32_t* d_srs_canon, const uint32_t* d_coeffs, size_t stride,
               unsigned log2n, size_t batch, bool bitrev, uint32_t* d_out_xy, uint32_t* d_out_inf, hipStream_t st);
 void prove_all_drop(Ctx* ctx);  // the SRS changed: every setup is stale
+// coset openings (multi-point FK20): the setup of (log2n, log2l), and the batch x R
+// proofs, R = 2^(log2n - log2l + ext) cosets of the size-D domain, D = R 2^log2l;
+// d_y (may be null): the batch x D values in coset order, or the bit-reversed
+// evaluation array with bitrev
+int prove_cosets_setup(Ctx* ctx, MsmWs& ws, const uint32_t* d_srs_canon, unsigned log2n, unsigned log2l,
+                       hipStream_t st);
+int prove_cosets(Ctx* ctx, MsmWs& ws, const uint32_t* d_srs_canon, const uint32_t* d_coeffs, size_t stride,
+                 unsigned log2n, unsigned log2l, size_t batch, bool ext, bool bitrev, uint32_t* d_out_xy,
+                 uint32_t* d_out_inf, uint32_t* d_y, hipStream_t st);
 
 // verify path: G2 SRS, polyeval_G2, pairing (pairing.hip)
 int gen_srs_g2_points(Ctx* ctx, const uint32_t* d_tau, size_t start, size_t n, uint32_t* d_out, hipStream_t st);

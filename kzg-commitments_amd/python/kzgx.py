@@ -40,6 +40,7 @@ EXPORTS = [
     "kzgx_commit_evals_batch_device", "kzgx_prove_evals_batch", "kzgx_prove_evals_batch_device",
     "kzgx_g1_ntt", "kzgx_g1_ntt_device", "kzgx_prove_all_prepare", "kzgx_prove_all_batch",
     "kzgx_prove_all_batch_device",
+    "kzgx_coset_points", "kzgx_prove_cosets_prepare", "kzgx_prove_cosets_batch", "kzgx_prove_cosets_batch_device",
 ]
 
 
@@ -60,6 +61,8 @@ NTT_TILE_LOG2 = _header_define("KZGX_NTT_TILE_LOG2")
 # per internal chunk of transforms
 PROVE_ALL_EVALS = _header_define("KZGX_PROVE_ALL_EVALS")
 G1_NTT_CHUNK_POINTS = _header_define("KZGX_G1_NTT_CHUNK_POINTS")
+# coset openings: the cosets are those of the size-2n domain
+PROVE_COSETS_EXTENDED = _header_define("KZGX_PROVE_COSETS_EXTENDED")
 
 _lib = None
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -183,6 +186,12 @@ def lib():
             "kzgx_prove_all_batch": (ctypes.c_int, [vp, u64p, ctypes.c_uint, sz, ctypes.c_int, u64p, intp, u64p]),
             "kzgx_prove_all_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, sz, ctypes.c_int, vp, vp, vp,
                                                            vp]),
+            "kzgx_coset_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_int, sz, u64p]),
+            "kzgx_prove_cosets_prepare": (ctypes.c_int, [vp, ctypes.c_uint, ctypes.c_uint]),
+            "kzgx_prove_cosets_batch": (ctypes.c_int, [vp, u64p, ctypes.c_uint, ctypes.c_uint, sz, ctypes.c_int, u64p,
+                                                       intp, u64p]),
+            "kzgx_prove_cosets_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, ctypes.c_uint, sz, sz,
+                                                              ctypes.c_int, vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -258,6 +267,20 @@ def domain_root(curve: str, log2n: int) -> int:
 
 def _ntt_flags(inverse: bool = False, bitrev: bool = False) -> int:
     return (NTT_INVERSE if inverse else 0) | (NTT_BITREV if bitrev else 0)
+
+
+def _cosets_flags(extended: bool = False, evals: bool = False, bitrev: bool = False) -> int:
+    return (PROVE_COSETS_EXTENDED if extended else 0) | (PROVE_ALL_EVALS if evals else 0) | _ntt_flags(bitrev=bitrev)
+
+
+def coset_points(curve: str, log2n: int, log2l: int, index: int, extended: bool = False,
+                 bitrev: bool = False) -> np.ndarray:
+    """kzgx_coset_points: the (2^log2l, 4) points whose values sit in chunk `index` of prove_cosets' y,
+    in y's order (host arithmetic, no device)"""
+    xs = np.zeros((1 << log2l, 4), dtype=np.uint64)
+    _chk(lib().kzgx_coset_points(CURVES[curve], log2n, log2l, _cosets_flags(extended, bitrev=bitrev), index, _p(xs)),
+         "kzgx_coset_points")
+    return xs
 
 
 def _log2_exact(n: int) -> int:
@@ -834,3 +857,36 @@ class Context:
         flags = _ntt_flags(bitrev=bitrev) | (PROVE_ALL_EVALS if evals else 0)
         _chk(lib().kzgx_prove_all_batch_device(self.h, d_in, log2n, batch, stride, flags, d_out, d_inf, d_y, stream),
              "kzgx_prove_all_batch_device")
+
+    # ---- coset (cell) openings ----
+    def prove_cosets_prepare(self, log2n: int, log2l: int):
+        """kzgx_prove_cosets_prepare: build the coset setup of (2^log2n coefficients, 2^log2l points) now."""
+        _chk(lib().kzgx_prove_cosets_prepare(self.h, log2n, log2l), "kzgx_prove_cosets_prepare")
+
+    def prove_cosets(self, polys, log2l: int, extended: bool = False, evals: bool = False, bitrev: bool = False,
+                     want_y: bool = True):
+        """kzgx_prove_cosets_batch: (n, 4) or (batch, n, 4) coefficients (evals: values on the size-n domain)
+        -> (xy (batch, R, 2 w64), is_inf (batch, R), y (batch, R, l, 4) or None), R = n / l cosets of
+        l = 2^log2l points, 2 n / l with extended; one polynomial drops the batch axis."""
+        c = np.ascontiguousarray(polys, dtype=np.uint64)
+        single = c.ndim == 2
+        if single:
+            c = c.reshape(1, -1, 4)
+        batch, n = c.shape[0], c.shape[1]
+        log2n = _log2_exact(n)
+        R = max(1, (n << int(bool(extended))) >> log2l)
+        out = np.zeros((batch, R, 2 * self.w64), dtype=np.uint64)
+        inf = np.zeros((batch, R), dtype=np.int32)
+        y = np.zeros((batch, R, 1 << log2l, 4), dtype=np.uint64) if want_y else None
+        flags = _cosets_flags(extended, evals, bitrev)
+        _chk(lib().kzgx_prove_cosets_batch(self.h, _p(c), log2n, log2l, batch, flags, _p(out),
+                                           inf.ctypes.data_as(intp), _p(y)), "kzgx_prove_cosets_batch")
+        inf = inf.astype(bool)
+        return (out[0], inf[0], None if y is None else y[0]) if single else (out, inf, y)
+
+    def prove_cosets_device(self, d_in, log2n, log2l, batch, stride, d_out, d_inf, d_y=None, extended=False,
+                            evals=False, bitrev=False, stream=None):
+        """kzgx_prove_cosets_batch_device: device pointers, stride in scalars, enqueued on stream."""
+        _chk(lib().kzgx_prove_cosets_batch_device(self.h, d_in, log2n, log2l, batch, stride,
+                                                  _cosets_flags(extended, evals, bitrev), d_out, d_inf, d_y, stream),
+             "kzgx_prove_cosets_batch_device")

@@ -171,6 +171,10 @@ class trusted_setup {
   G1 polyeval_G1(const std::vector<Fr>& P);
   bool aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
                   const std::vector<std::pair<Fr, Fr>>& points, bool checked, bool check_subgroup);
+  bool coset_aggregated(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
+                        const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
+                        const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended, bool bit_reversed,
+                        bool checked, bool check_subgroup);
 
  public:
   /** random tau (std::random_device), [tau^i]G1 and [tau^i]G2 for
@@ -269,6 +273,33 @@ class trusted_setup {
    *  fails, whatever the pairing equation says. */
   bool verify_proofs_aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
                                 const std::vector<std::pair<Fr, Fr>>& points, bool check_subgroup);
+  /** Extension: one pairing check for many coset openings (cells) of several
+   *  commitments (kzgx_verify_cells_aggregate with library-drawn 128-bit
+   *  challenges).  Cell k opens commits[commit_index[k]] on coset cell_index[k]
+   *  of create_coset_proofs' layout for (log2n, extended), with proofs[k] and
+   *  the 2^log2l values values[k] in the coset's point order; log2l is taken
+   *  from the values' length.  With bit_reversed cell_index[k] is the element
+   *  number of create_coset_proofs(..., bit_reversed = true) and values[k] the
+   *  matching chunk of the bit-reversed evaluation array, as they come.  Each
+   *  commitment is passed once.  True iff every cell verifies (false-accept
+   *  probability <= 2^-128); on false, verify_proof per cell (over the points
+   *  kzgx_coset_points lists) says which.  An empty batch is true.  Needs
+   *  only 2^log2l G1 and 2^log2l + 1 G2 setup points, whatever log2n.
+   *  @throws std::invalid_argument on mismatched sizes, values whose length is
+   *          not one power of two shared by all cells, an index out of range,
+   *          log2l > log2n, or a domain beyond the curve's */
+  bool verify_coset_proofs(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
+                           const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
+                           const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended = false,
+                           bool bit_reversed = false);
+  /** Extension: the same behind a validation of every commit and proof
+   *  (kzgx_verify_cells_aggregate_checked): canonical and on the curve, and
+   *  with check_subgroup in the prime-order subgroup; false as soon as one
+   *  point fails, whatever the pairing equation says. */
+  bool verify_coset_proofs(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
+                           const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
+                           const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
+                           bool bit_reversed, bool check_subgroup);
   /** Extension: every installed G1 and G2 point is canonical, on its curve
    *  and (subgroup) in the prime-order subgroup (kzgx_srs_check, on the
    *  device).  trusted_setup(filename) tests on-curve only: call this after

@@ -24,7 +24,8 @@
  * kzgx_g1_ntt*, kzgx_prove_all_*: the same transform over G1 points, and all n
  * openings of a polynomial on its size-n domain in Theta(n log n) group operations;
  * kzgx_prove_cosets_*, kzgx_coset_points: one opening per coset (cell) of that
- * domain or of the twice larger one, all cosets at once.
+ * domain or of the twice larger one, all cosets at once;
+ * kzgx_verify_cells_aggregate*: one pairing check for many such cells.
  *
  * Conventions
  *   - plain pointers and sizes only; no torch / HIP types in signatures
@@ -607,6 +608,99 @@ int kzgx_prove_cosets_batch(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, u
 int kzgx_prove_cosets_batch_device(kzgx_ctx* ctx, const void* d_in, unsigned log2n, unsigned log2l, size_t batch,
                                    size_t in_stride, int flags, void* d_out_xy, void* d_out_is_inf, void* d_y,
                                    void* stream);
+
+/* ---- aggregated cell verification (extension) -------------------------------------------
+ * One pairing check for count coset openings ("cells") of n_commits commitments,
+ * the consumer side of kzgx_prove_cosets_batch.  Notation as above: n = 2^log2n,
+ * l = 2^log2l, ext = 1 with KZGX_PROVE_COSETS_EXTENDED else 0, R = 2^(log2n - log2l
+ * + ext) cosets of the size-D domain, D = R l, w = kzgx_domain_root(curve, log2 D),
+ * coset i = {w^(i + R j), j < l} = the roots of X^l - a_i, a_i = w^(i l).  Cell k is
+ * (commitment c_k, coset i_k, proof pi_k, values y_kj = claimed P(x(i_k, j)),
+ * challenge r_k).  Its interpolant of degree < l is
+ *   I_k(X) = sum_t w^(-i_k t) INTT_l(y_k)[t] X^t
+ * (INTT_l: kzgx_ntt with KZGX_NTT_INVERSE at size l), and the call computes
+ *   S_t   = sum_k r_k w^(-i_k t) INTT_l(y_k)[t]                      (t < l)
+ *   rho_c = sum_{k : c_k = c} r_k                                    (c < n_commits)
+ *   A     = sum_k r_k pi_k
+ *   B     = sum_c rho_c C_c + sum_k (r_k a_(i_k)) pi_k - sum_t S_t G1[t]
+ *   *ok   = e(A, G2[l]) == e(B, G2[0])
+ * -- one batched size-l inverse NTT, a fold over the cells, two variable-base MSMs
+ * (count points; n_commits + count + l points) and ONE two-pairing product; no
+ * interpolation over arbitrary points and no G2 MSM.  With log2l = 0 this is
+ * kzgx_verify_aggregate's equation at z_k = w^(i_k).  No reference counterpart.
+ *  commits: n_commits distinct commitments, each passed once (unused ones are
+ *   harmless); commit_index[k] < n_commits names cell k's.  proofs: count points.
+ *   ys: count x l canonical scalars, packed.  Infinity as in kzgx_msm_g1_points
+ *   (all-zero or a set flag; the flag arrays may be NULL).
+ *  flags: KZGX_NTT_BITREV and KZGX_PROVE_COSETS_EXTENDED only.  Without
+ *   KZGX_NTT_BITREV cell_index[k] is the coset i and ys[k] is in the order j = 0 ..
+ *   l - 1: the natural output of kzgx_prove_cosets_batch.  With it cell_index[k] is
+ *   the chunk number p of the bit-reversed size-D evaluation array -- the coset is
+ *   brev_R(p) and the l values are in bit-reversed order -- so proof p and y[p] of
+ *   kzgx_prove_cosets_batch(..., KZGX_NTT_BITREV) are passed as they come, and
+ *   kzgx_coset_points with the same flags and index lists the cell's points.
+ *  challenges: count x 4 uint64 canonical scalars, as in kzgx_verify_aggregate:
+ *   explicit ones make the answer a deterministic function of the inputs (the
+ *   equation above, nothing else); NULL (host entries only) lets the library draw
+ *   independent 128-bit values, r_0 = 1; NULL on a device entry is KZGX_ERR_ARG.
+ *   The equivalence with the AND of the per-cell kzgx_verify_proof calls is
+ *   kzgx_verify_aggregate's: equal when every cell is valid, and whenever exactly
+ *   one is invalid under nonzero challenges; errors can cancel under challenges
+ *   the prover predicts.  Which cell failed is not reported: kzgx_verify_proof per
+ *   cell says.
+ *  Setup: a G1 SRS of at least l points with G1[t] = [tau^t]G for t < l, and a G2
+ *   setup of at least l + 1 points.  The call never touches n SRS points, so
+ *   2^log2n may exceed the installed SRS: a verifier of the data-availability
+ *   shape (log2n = 12, log2l = 6, extended) needs 64 G1 and 65 G2 points.
+ *  Points are taken as canonical and on the curve, as in kzgx_verify_aggregate.
+ *   The _checked forms first run the G1 check of kzgx_g1_check_batch over the
+ *   n_commits commitments and the count proofs and force *ok = 0 when one fails,
+ *   exactly like kzgx_verify_aggregate_checked(_device).
+ *  Device entries: device pointers (indices and infinity flags uint32, d_ok one
+ *   uint32), asynchronous on stream (NULL = the context's), no host read-back.
+ *   An index out of range (commit_index >= n_commits, cell_index >= R) reads
+ *   nothing out of bounds and forces *d_ok = 0 (a flag folded on the device).
+ *  Workspace: count x l scalars for the transforms plus the MSMs'; count x l is
+ *   capped at KZGX_VERIFY_CELLS_VALUES_MAX (512 MiB of scalars).
+ *  When it pays (BLS12-381, MI355X, profiles/verify_cells.json, DESIGN.md "Cell
+ *   verification"): at (12, 6) extended, bit-reversed, a device call costs about
+ *   10 ms whatever it carries -- 128 cells 9.9 ms, 1024 cells 9.7 ms, 8192 cells of
+ *   64 blobs 10.4 ms (788k cells/s) -- against 4.05 ms per kzgx_verify_proof call of
+ *   one cell (host wall clock): 519, 4155 and 33152 ms, x52, x430 and x3189.  The
+ *   call is latency-bound: the two MSMs' window sums and Horner steps take about
+ *   7 ms and the pairing product 3 ms at every count, the fold kernels 0.03 to
+ *   0.15 ms (0.3% to 1.5% of the call) and the inverse NTTs 0.03 to 0.04 ms.  Only a
+ *   call of 1 or 2 cells is SLOWER than the separate calls (the crossover is at
+ *   2.4 calls' worth).  The checked form with the subgroup test costs x1.15 at
+ *   8192 cells (11.7 against 10.2 ms).  No path is chosen silently.
+ *  Statuses: log2l > log2n or log2n + ext > kzgx_ntt_max_log2(curve), an unknown
+ *   flag (KZGX_NTT_INVERSE and KZGX_PROVE_ALL_EVALS included), a NULL required
+ *   pointer, n_commits + count + l > KZGX_MSM_POINTS_MAX, count x l >
+ *   KZGX_VERIFY_CELLS_VALUES_MAX, and on the host entries an index >= n_commits or
+ *   >= R: KZGX_ERR_ARG; no G1 SRS or fewer than l + 1 G2 points: KZGX_ERR_NO_SRS;
+ *   fewer than l G1 points: KZGX_ERR_DEGREE; count == 0: *ok = 1 (n_commits may
+ *   then be 0). */
+#define KZGX_VERIFY_CELLS_VALUES_MAX ((size_t)1 << 24)
+int kzgx_verify_cells_aggregate(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                                const uint32_t* commit_index, const uint32_t* cell_index, const uint64_t* proofs_xy,
+                                const int* proof_inf, const uint64_t* ys, const uint64_t* challenges, size_t count,
+                                unsigned log2n, unsigned log2l, int flags, int* ok);
+int kzgx_verify_cells_aggregate_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                       size_t n_commits, const void* d_commit_index, const void* d_cell_index,
+                                       const void* d_proofs, const void* d_proof_inf, const void* d_ys,
+                                       const void* d_challenges, size_t count, unsigned log2n, unsigned log2l,
+                                       int flags, void* d_ok, void* stream);
+int kzgx_verify_cells_aggregate_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf,
+                                        size_t n_commits, const uint32_t* commit_index, const uint32_t* cell_index,
+                                        const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* ys,
+                                        const uint64_t* challenges, size_t count, unsigned log2n, unsigned log2l,
+                                        int flags, int subgroup, int* ok);
+int kzgx_verify_cells_aggregate_checked_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                               size_t n_commits, const void* d_commit_index,
+                                               const void* d_cell_index, const void* d_proofs,
+                                               const void* d_proof_inf, const void* d_ys, const void* d_challenges,
+                                               size_t count, unsigned log2n, unsigned log2l, int flags, int subgroup,
+                                               void* d_ok, void* stream);
 
 #ifdef __cplusplus
 }

@@ -224,4 +224,16 @@ KZGX_DEV void fe_store(uint32_t* p, const Fe<FP>& a) {
   }
 }
 
+
+// Fr NTT twiddles (ntt.hip builds the table: w^j of the 2^K-th root, j <= 2^(K-1),
+// Montgomery form): w_m^(+-e) for e < m = 2^lm, K >= lm >= 1
+template <class FR>
+KZGX_DEV Fe<FR> ntt_tw(const uint32_t* __restrict__ table, uint32_t K, uint32_t lm, uint32_t e, bool inverse) {
+  const uint32_t m = 1u << lm, h = m >> 1;
+  if (inverse) e = (m - e) & (m - 1);
+  const bool neg = e >= h;  // w^(m/2) = -1
+  const Fe<FR> v = fe_load<FR>(table + ((size_t)(neg ? e - h : e) << (K - lm)) * FR::N);
+  return neg ? fe_neg<FR>(v) : v;
+}
+
 }  // namespace kzgx

@@ -873,6 +873,78 @@ bool trusted_setup::aggregated(std::vector<commit>& commits, std::vector<proof>&
   return ok != 0;
 }
 
+bool trusted_setup::verify_coset_proofs(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
+                                        const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
+                                        const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
+                                        bool bit_reversed) {
+  return coset_aggregated(commits, commit_index, cell_index, proofs, values, log2n, extended, bit_reversed, false,
+                          false);
+}
+
+bool trusted_setup::verify_coset_proofs(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
+                                        const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
+                                        const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
+                                        bool bit_reversed, bool check_subgroup) {
+  return coset_aggregated(commits, commit_index, cell_index, proofs, values, log2n, extended, bit_reversed, true,
+                          check_subgroup);
+}
+
+bool trusted_setup::coset_aggregated(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
+                                     const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
+                                     const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
+                                     bool bit_reversed, bool checked, bool check_subgroup) {
+  const size_t m = proofs.size(), nc = commits.size();
+  if (commit_index.size() != m || cell_index.size() != m || values.size() != m)
+    throw std::invalid_argument("verify_coset_proofs: size mismatch");
+  if (m == 0) return true;
+  const size_t l = values[0].size();
+  if (l == 0 || (l & (l - 1))) throw std::invalid_argument("verify_coset_proofs: a cell's size is not a power of two");
+  unsigned kl = 0;
+  while (((size_t)1 << kl) < l) kl++;
+  const int mx = kzgx_ntt_max_log2(g_curve), ext = extended ? 1 : 0;
+  if (kl > log2n) throw std::invalid_argument("verify_coset_proofs: a coset larger than the domain");
+  if (log2n > 31 || (int)log2n + ext > mx)
+    throw std::invalid_argument("verify_coset_proofs: the opened domain exceeds the curve's power-of-two domain");
+  const size_t R = (size_t)1 << (log2n - kl + ext);
+  for (size_t k = 0; k < m; k++) {
+    if (values[k].size() != l) throw std::invalid_argument("verify_coset_proofs: cells of different sizes");
+    if (commit_index[k] >= nc || cell_index[k] >= R)
+      throw std::invalid_argument("verify_coset_proofs: index out of range");
+  }
+  const int nl = base_limbs();
+  std::vector<uint64_t> c(2 * nl * nc, 0), p(2 * nl * m, 0), y(4 * m * l);
+  std::vector<int> ci(nc), pi(m);
+  for (size_t k = 0; k < nc; k++) {
+    const G1& cg = commits[k].get_curve_point();
+    for (int i = 0; i < nl; i++) {
+      c[2 * nl * k + i] = cg.x[i];
+      c[2 * nl * k + nl + i] = cg.y[i];
+    }
+    ci[k] = cg.inf;
+  }
+  for (size_t k = 0; k < m; k++) {
+    const G1& pg = proofs[k].get_curve_point();
+    for (int i = 0; i < nl; i++) {
+      p[2 * nl * k + i] = pg.x[i];
+      p[2 * nl * k + nl + i] = pg.y[i];
+    }
+    pi[k] = pg.inf;
+    for (size_t j = 0; j < l; j++) std::memcpy(&y[4 * (k * l + j)], values[k][j].v.data(), 32);
+  }
+  const int flags = (extended ? KZGX_PROVE_COSETS_EXTENDED : 0) | (bit_reversed ? KZGX_NTT_BITREV : 0);
+  int ok = 0;
+  if (checked)
+    check(kzgx_verify_cells_aggregate_checked(ctx, c.data(), ci.data(), nc, commit_index.data(), cell_index.data(),
+                                              p.data(), pi.data(), y.data(), nullptr, m, log2n, kl, flags,
+                                              check_subgroup ? 1 : 0, &ok),
+          "kzgx_verify_cells_aggregate_checked");
+  else
+    check(kzgx_verify_cells_aggregate(ctx, c.data(), ci.data(), nc, commit_index.data(), cell_index.data(), p.data(),
+                                      pi.data(), y.data(), nullptr, m, log2n, kl, flags, &ok),
+          "kzgx_verify_cells_aggregate");
+  return ok != 0;
+}
+
 G1 trusted_setup::linear_combination(const std::vector<G1>& points, const std::vector<Fr>& scalars) {
   const size_t m = points.size();
   if (scalars.size() != m) throw std::invalid_argument("linear_combination: size mismatch");

@@ -2337,6 +2337,210 @@ int kzgx_prove_cosets_batch(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, u
 
 }  // extern "C"
 
+// ---- aggregated cell verification -----------------------------------------------------------
+namespace {
+struct CellsShape {
+  unsigned kR, kD;  // log2 of the cosets and of the domain they partition
+  size_t l;
+  bool bitrev;
+};
+
+// the argument, limit and setup checks shared by the four entries
+int cells_args(kzgx_ctx* ctx, size_t n_commits, size_t count, unsigned log2n, unsigned log2l, int flags,
+               CellsShape* s) {
+  const int mx = kzgx::ntt_max_log2(ctx->c.curve);
+  if (flags & ~(KZGX_NTT_BITREV | KZGX_PROVE_COSETS_EXTENDED)) return KZGX_ERR_ARG;
+  const int ext = (flags & KZGX_PROVE_COSETS_EXTENDED) ? 1 : 0;
+  if (mx < 0 || log2n > 31 || log2l > log2n || (int)log2n + ext > mx) return KZGX_ERR_ARG;
+  s->kR = log2n - log2l + ext;
+  s->kD = log2n + ext;
+  s->l = (size_t)1 << log2l;
+  s->bitrev = (flags & KZGX_NTT_BITREV) != 0;
+  if (n_commits > KZGX_MSM_POINTS_MAX || count > KZGX_MSM_POINTS_MAX ||
+      n_commits + count + s->l > KZGX_MSM_POINTS_MAX)
+    return KZGX_ERR_ARG;
+  if ((count << log2l) > KZGX_VERIFY_CELLS_VALUES_MAX) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0 || ctx->n_srs2 < s->l + 1) return KZGX_ERR_NO_SRS;
+  if (ctx->c.n_srs < s->l) return KZGX_ERR_DEGREE;
+  return KZGX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kzgx_verify_cells_aggregate_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                       size_t n_commits, const void* d_commit_index, const void* d_cell_index,
+                                       const void* d_proofs, const void* d_proof_inf, const void* d_ys,
+                                       const void* d_challenges, size_t count, unsigned log2n, unsigned log2l,
+                                       int flags, void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (!d_ok || !d_challenges) return KZGX_ERR_ARG;
+  if (count > 0 && (!d_commit_index || !d_cell_index || !d_proofs || !d_ys || (n_commits > 0 && !d_commits)))
+    return KZGX_ERR_ARG;
+  CellsShape sh;
+  KZGX_TRY(cells_args(ctx, n_commits, count, log2n, log2l, flags, &sh));
+  hipStream_t st = pick(ctx, stream);
+  if (count == 0) {
+    KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)d_ok, 1, 1, st));
+    return KZGX_OK;
+  }
+  kzgx::Ctx* c = &ctx->c;
+  kzgx::WsLease ws = c->ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const size_t pw = point_words(ctx), l = sh.l, nsl = kzgx::cells_fold_slices(count, log2l);
+  // the cells' interpolants; rho | s | -S (+ the fold's partials and flags);
+  // A | B | their flags, the index gate | G2[l], G2[0] | the pairing's line tables
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->ntt_coef, count * l * 32, &ws->ntt_coef_b));
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->var_scal, (n_commits + count + l + nsl * l) * 32 + nsl * 4,
+                           &ws->var_scal_b));
+  const size_t o_q = 2 * pw + 8, o_ln = (o_q + 4 * pw + 63) & ~(size_t)63;
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->var_pt, o_ln * 4 + kzgx::pair2_wave_scratch_bytes(c->curve),
+                           &ws->var_pt_b));
+  uint32_t* A = ws->var_pt;
+  uint32_t* B = A + pw;
+  uint32_t* fl = B + pw;  // [A_inf, B_inf, -, -, gate]
+  uint32_t* gate = fl + 4;
+  uint32_t* q = A + o_q;
+  // I_k's coefficients up to the coset shift: the size-l inverse transforms of the values
+  KZGX_TRY(kzgx::ntt_twiddles(c, sh.kD, st));
+  KZGX_TRY(kzgx::ntt(c, (const uint32_t*)d_ys, l, ws->ntt_coef, l, log2l, count, true, sh.bitrev, st));
+  KZGX_TRY(kzgx::cells_scalars(c, ws->ntt_coef, (const uint32_t*)d_challenges, (const uint32_t*)d_cell_index,
+                               (const uint32_t*)d_commit_index, count, n_commits, log2l, sh.kD, sh.bitrev,
+                               ws->var_scal, gate, st));
+  // A = sum r_k proof_k
+  const kzgx::PointSeg sa{(const uint32_t*)d_proofs, (const uint32_t*)d_proof_inf, count};
+  KZGX_TRY(kzgx::msm_points(c, *ws, &sa, 1, (const uint32_t*)d_challenges, A, fl, st));
+  // B = sum rho_c commit_c + sum r_k a_k proof_k - sum S_t G1[t]
+  const kzgx::PointSeg sb[3] = {{(const uint32_t*)d_commits, (const uint32_t*)d_commit_inf, n_commits},
+                                {(const uint32_t*)d_proofs, (const uint32_t*)d_proof_inf, count},
+                                {ctx->d_srs_canon, nullptr, l}};
+  KZGX_TRY(kzgx::msm_points(c, *ws, sb, 3, ws->var_scal, B, fl + 1, st));
+  // e(A, G2[l]) e(-B, G2[0]) == 1, every case decided on the device; then the index gate
+  const size_t p2 = 2 * pw * 4;
+  KZGX_TRY_HIP(hipMemcpyAsync(q, (const char*)ctx->d_srs2_canon + l * p2, p2, hipMemcpyDeviceToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync((char*)q + p2, ctx->d_srs2_canon, p2, hipMemcpyDeviceToDevice, st));
+  KZGX_TRY(kzgx::pair2_wave(c, A, fl, q, nullptr, A + o_ln, (uint32_t*)d_ok, st));
+  return kzgx::flag_gate((uint32_t*)d_ok, gate, st);
+}
+
+int kzgx_verify_cells_aggregate_checked_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                               size_t n_commits, const void* d_commit_index,
+                                               const void* d_cell_index, const void* d_proofs,
+                                               const void* d_proof_inf, const void* d_ys, const void* d_challenges,
+                                               size_t count, unsigned log2n, unsigned log2l, int flags, int subgroup,
+                                               void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (!d_ok || !d_challenges) return KZGX_ERR_ARG;
+  if (count > 0 && (!d_commit_index || !d_cell_index || !d_proofs || !d_ys || (n_commits > 0 && !d_commits)))
+    return KZGX_ERR_ARG;
+  CellsShape sh;
+  KZGX_TRY(cells_args(ctx, n_commits, count, log2n, log2l, flags, &sh));
+  hipStream_t st = pick(ctx, stream);
+  if (count == 0) {
+    KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)d_ok, 1, 1, st));
+    return KZGX_OK;
+  }
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const size_t np = n_commits + count;
+  uint32_t* f;  // commit flags | proof flags | their AND
+  KZGX_TRY(chk_scratch(ctx, ws, np + 1, &f));
+  KZGX_TRY(kzgx::g1_check2(&ctx->c, (const uint32_t*)d_commits, (const uint32_t*)d_commit_inf, n_commits,
+                           (const uint32_t*)d_proofs, (const uint32_t*)d_proof_inf, count, subgroup, f, st));
+  KZGX_TRY(kzgx::flags_and(f, np, f + np, st));
+  KZGX_TRY(kzgx_verify_cells_aggregate_device(ctx, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index,
+                                              d_proofs, d_proof_inf, d_ys, d_challenges, count, log2n, log2l, flags,
+                                              d_ok, stream));
+  return kzgx::flag_gate((uint32_t*)d_ok, f + np, st);
+}
+
+}  // extern "C"
+
+// the host-pointer forms share the staging, the index checks and the drawn challenges
+static int verify_cells_host(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                             const uint32_t* commit_index, const uint32_t* cell_index, const uint64_t* proofs_xy,
+                             const int* proof_inf, const uint64_t* ys, const uint64_t* challenges, size_t count,
+                             unsigned log2n, unsigned log2l, int flags, bool checked, int subgroup, int* ok) {
+  KZGX_TRY(activate(ctx));
+  if (!ok) return KZGX_ERR_ARG;
+  if (count > 0 && (!commit_index || !cell_index || !proofs_xy || !ys || (n_commits > 0 && !commits_xy)))
+    return KZGX_ERR_ARG;
+  CellsShape sh;
+  KZGX_TRY(cells_args(ctx, n_commits, count, log2n, log2l, flags, &sh));
+  if (count == 0) {
+    *ok = 1;
+    return KZGX_OK;
+  }
+  for (size_t k = 0; k < count; k++)
+    if (commit_index[k] >= n_commits || (cell_index[k] >> sh.kR)) return KZGX_ERR_ARG;
+  // library-drawn challenges: independent 128-bit values, r_0 = 1 (as kzgx_verify_aggregate)
+  std::vector<uint64_t> drawn;
+  if (!challenges) {
+    drawn.assign(count * 4, 0);
+    std::random_device rd;
+    for (size_t k = 0; k < count; k++)
+      for (int j = 0; j < 2; j++) drawn[4 * k + j] = ((uint64_t)rd() << 32) | (uint64_t)rd();
+    drawn[0] = 1;
+    drawn[1] = 0;
+    challenges = drawn.data();
+  }
+  const size_t pb = point_words(ctx) * 4, yb = count * sh.l * 32, np = n_commits + count;
+  void *d_c, *d_p, *d_s, *d_f;
+  KZGX_TRY(stage(ctx, 0, n_commits * pb + 16, &d_c));
+  KZGX_TRY(stage(ctx, 1, count * pb, &d_p));
+  KZGX_TRY(stage(ctx, 2, yb + count * 32, &d_s));
+  KZGX_TRY(stage(ctx, 3, (np + 2 * count) * 4 + 16, &d_f));
+  // commit flags | proof flags | commit_index | cell_index | ok
+  std::vector<uint32_t> fl(np + 2 * count);
+  for (size_t k = 0; k < n_commits; k++) fl[k] = commit_inf ? (uint32_t)(commit_inf[k] != 0) : 0u;
+  for (size_t k = 0; k < count; k++) {
+    fl[n_commits + k] = proof_inf ? (uint32_t)(proof_inf[k] != 0) : 0u;
+    fl[np + k] = commit_index[k];
+    fl[np + count + k] = cell_index[k];
+  }
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_c, commits_xy, n_commits * pb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_p, proofs_xy, count * pb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_s, ys, yb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync((char*)d_s + yb, challenges, count * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_f, fl.data(), fl.size() * 4, hipMemcpyHostToDevice, st));
+  uint32_t* f = (uint32_t*)d_f;
+  uint32_t* d_ok = f + np + 2 * count;
+  if (checked)
+    KZGX_TRY(kzgx_verify_cells_aggregate_checked_device(ctx, d_c, f, n_commits, f + np, f + np + count, d_p,
+                                                        f + n_commits, d_s, (char*)d_s + yb, count, log2n, log2l,
+                                                        flags, subgroup, d_ok, nullptr));
+  else
+    KZGX_TRY(kzgx_verify_cells_aggregate_device(ctx, d_c, f, n_commits, f + np, f + np + count, d_p, f + n_commits,
+                                                d_s, (char*)d_s + yb, count, log2n, log2l, flags, d_ok, nullptr));
+  uint32_t v = 0;
+  KZGX_TRY_HIP(hipMemcpyAsync(&v, d_ok, 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  *ok = v ? 1 : 0;
+  return KZGX_OK;
+}
+
+extern "C" {
+
+int kzgx_verify_cells_aggregate(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                                const uint32_t* commit_index, const uint32_t* cell_index, const uint64_t* proofs_xy,
+                                const int* proof_inf, const uint64_t* ys, const uint64_t* challenges, size_t count,
+                                unsigned log2n, unsigned log2l, int flags, int* ok) {
+  return verify_cells_host(ctx, commits_xy, commit_inf, n_commits, commit_index, cell_index, proofs_xy, proof_inf, ys,
+                           challenges, count, log2n, log2l, flags, false, 0, ok);
+}
+
+int kzgx_verify_cells_aggregate_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf,
+                                        size_t n_commits, const uint32_t* commit_index, const uint32_t* cell_index,
+                                        const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* ys,
+                                        const uint64_t* challenges, size_t count, unsigned log2n, unsigned log2l,
+                                        int flags, int subgroup, int* ok) {
+  return verify_cells_host(ctx, commits_xy, commit_inf, n_commits, commit_index, cell_index, proofs_xy, proof_inf, ys,
+                           challenges, count, log2n, log2l, flags, true, subgroup, ok);
+}
+
+}  // extern "C"
+
 namespace {
 // Once both SRS halves are present (the end of trusted_setup(int) or of a
 // setup-file load): the verify tables (kzgx_verify_proof's [y]G table and the

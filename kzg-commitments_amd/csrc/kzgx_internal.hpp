@@ -360,6 +360,15 @@ int msm_points(Ctx* ctx, MsmWs& ws, const PointSeg* segs, int nseg, const uint32
 // followed by 256 scalars of scratch for the block sums)
 int aggregate_scalars(Ctx* ctx, const uint32_t* d_z, const uint32_t* d_y, const uint32_t* d_r, size_t n,
                       uint32_t* d_out, hipStream_t st);
+// verify_cells_aggregate's scalars (poly.hip): from d_T = the count x l inverse transforms of the cells'
+// values, d_out = rho_c (n_commits) | s_k = r_k a_(i_k) (count) | -S_t (l), followed by
+// cells_fold_slices(count, log2l) * l scalars and as many words of scratch; *d_gate = 1 iff every
+// commit_index < n_commits and every cell_index < R = 2^(log2D - log2l).  The twiddle table of the
+// size-2^log2D domain must be built (ntt_twiddles) with st ordered behind it.
+size_t cells_fold_slices(size_t count, unsigned log2l);
+int cells_scalars(Ctx* ctx, const uint32_t* d_T, const uint32_t* d_r, const uint32_t* d_cell_index,
+                  const uint32_t* d_commit_index, size_t count, size_t n_commits, unsigned log2l, unsigned log2D,
+                  bool bitrev, uint32_t* d_out, uint32_t* d_gate, hipStream_t st);
 // one MSM as an XYZZ record, no affine conversion (msm.hip)
 int msm_partial_xyzz(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t* d_rec, hipStream_t st);
 int gen_srs_points(Ctx* ctx, const uint32_t* tau_canon_host, size_t start, size_t n, uint32_t* d_out_canon,

@@ -77,15 +77,7 @@ __global__ __launch_bounds__(256) void k_ntt_twiddles(NttRoots roots, uint32_t K
   fe_store<FR>(table + (size_t)j * FR::N, acc);
 }
 
-// w_m^(+-e) for e < m = 2^lm, from the table of the 2^K-th root (K >= lm >= 1)
-template <class FR>
-KZGX_DEV Fe<FR> ntt_tw(const uint32_t* __restrict__ table, uint32_t K, uint32_t lm, uint32_t e, bool inverse) {
-  const uint32_t m = 1u << lm, h = m >> 1;
-  if (inverse) e = (m - e) & (m - 1);
-  const bool neg = e >= h;  // w^(m/2) = -1
-  const Fe<FR> v = fe_load<FR>(table + ((size_t)(neg ? e - h : e) << (K - lm)) * FR::N);
-  return neg ? fe_neg<FR>(v) : v;
-}
+// (ntt_tw, the table lookup w_m^(+-e), is in field.hpp: poly.hip's cell fold reads the table too)
 
 enum NttMode : uint32_t { NTT_WHOLE = 0, NTT_COLS = 1, NTT_ROWS = 2 };
 

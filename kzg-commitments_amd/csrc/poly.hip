@@ -859,6 +859,163 @@ int aggregate_scalars(Ctx* ctx, const uint32_t* d_z, const uint32_t* d_y, const 
                                         : aggregate_scalars_impl<BLS12381Fr>(d_z, d_y, d_r, n, d_out, st);
 }
 
+// --------------------------------------------------------------------------
+// aggregated cell verification: the scalars of B's MSM (kzgx_verify_cells_aggregate)
+// --------------------------------------------------------------------------
+// T[k][t] = INTT_l(y_k)[t] (canonical), r_k canonical, coset i_k of the size-D
+// domain (D = R l, w = w_D):
+//   S_t = sum_k r_k w^(-i_k t) T[k][t],   s_k = r_k a_(i_k),  a_i = w^(i l),
+//   rho_c = sum_{k : c_k = c} r_k
+// out = rho_0..rho_{nc-1} | s_0..s_{count-1} | -S_0..-S_{l-1}, all canonical.
+// The twiddles are read from the Fr NTT's table (ntt_tw), never exponentiated.
+//
+// k_cells_fold: threads along t (lt = min(l, 256) of them, so a wave reads
+// consecutive scalars of a row of T), 256 / lt cells side by side in a
+// workgroup, blockIdx.x the column tile, blockIdx.y the slice of cells
+// (strided over gridDim.y slices).  A workgroup folds its cells' rows through
+// LDS into one partial per column, part[slice][t]; the first column tile also
+// writes s_k and ORs "cell k names a coset >= R or a commitment >= nc" into
+// bad_part[slice].  An index out of range reads nothing out of bounds: the
+// coset is reduced mod R before it picks a twiddle, the commitment index is
+// only compared.  k_cells_total: one lane per column adds the slices in
+// order, negates and writes -S_t; its first wave folds the bad flags into
+// *gate (1 = every index in range).  No atomics, no host round trip.
+constexpr uint32_t CELLS_SLICES = 128;
+
+size_t cells_fold_slices(size_t count, unsigned log2l) {
+  const size_t rows = (size_t)256 >> std::min(log2l, 8u);
+  return std::min<size_t>((count + rows - 1) / rows, CELLS_SLICES);
+}
+
+template <class FR>
+__global__ __launch_bounds__(256) void k_cells_fold(const uint32_t* __restrict__ T, const uint32_t* __restrict__ r,
+                                                    const uint32_t* __restrict__ cell_index,
+                                                    const uint32_t* __restrict__ commit_index, uint32_t count,
+                                                    uint32_t n_commits, uint32_t kl, uint32_t kD, uint32_t bitrev,
+                                                    const uint32_t* __restrict__ table, uint32_t K,
+                                                    uint32_t* __restrict__ s_out, uint32_t* __restrict__ part,
+                                                    uint32_t* __restrict__ bad_part) {
+  constexpr int N = FR::N;
+  __shared__ uint32_t lds[256 * N];
+  const uint32_t kR = kD - kl, R = 1u << kR, D = 1u << kD;
+  const uint32_t lgt = kl < 8 ? kl : 8, lt = 1u << lgt, rows = 256u >> lgt;
+  const uint32_t tx = threadIdx.x & (lt - 1), ty = threadIdx.x >> lgt;
+  const uint32_t t = blockIdx.x * lt + tx;  // < l: l is a multiple of lt
+  const bool first = blockIdx.x == 0 && tx == 0;
+  Fe<FR> acc = fe_zero<FR>();
+  int bad = 0;
+  for (uint32_t k = blockIdx.y * rows + ty; k < count; k += gridDim.y * rows) {
+    const uint32_t p = cell_index[k];
+    // chunk p of the bit-reversed evaluation array is coset brev_R(p)
+    const uint32_t i = bitrev ? (kR ? __brev(p) >> (32 - kR) : 0u) : p & (R - 1);
+    const Fe<FR> rc = fe_load<FR>(r + (size_t)k * N);
+    // w^(-i t) (D == 1: the table has no size-1 domain, and the twiddle is 1)
+    const Fe<FR> tw =
+        kD ? ntt_tw<FR>(table, K, kD, (uint32_t)(((uint64_t)i * t) & (D - 1)), true) : fe_one<FR>();
+    const Fe<FR> v = fe_mul<FR>(fe_load<FR>(T + (((size_t)k << kl) + t) * N), tw);  // canonical
+    acc = fe_add<FR>(acc, fe_mul<FR>(v, fe_to_mont<FR>(rc)));
+    if (first) {
+      bad |= (p >= R) | (commit_index[k] >= n_commits);
+      const Fe<FR> a =
+          kD ? ntt_tw<FR>(table, K, kD, (uint32_t)(((uint64_t)i << kl) & (D - 1)), false) : fe_one<FR>();
+      fe_store<FR>(s_out + (size_t)k * N, fe_mul<FR>(rc, a));
+    }
+  }
+  fe_store<FR>(lds + threadIdx.x * N, acc);
+  __syncthreads();
+  for (uint32_t s = rows >> 1; s >= 1; s >>= 1) {  // rows ty + s onto rows ty < s
+    if (ty < s) {
+      acc = fe_add<FR>(acc, fe_load<FR>(lds + (threadIdx.x + s * lt) * N));
+      fe_store<FR>(lds + threadIdx.x * N, acc);
+    }
+    __syncthreads();
+  }
+  if (ty == 0) fe_store<FR>(part + (((size_t)blockIdx.y << kl) + t) * N, acc);
+  const int any_bad = __syncthreads_or(bad);
+  if (blockIdx.x == 0 && threadIdx.x == 0) bad_part[blockIdx.y] = any_bad ? 1u : 0u;
+}
+
+template <class FR>
+__global__ __launch_bounds__(64) void k_cells_total(const uint32_t* __restrict__ part,
+                                                    const uint32_t* __restrict__ bad_part, uint32_t nslices,
+                                                    uint32_t l, uint32_t* __restrict__ neg_s,
+                                                    uint32_t* __restrict__ gate) {
+  constexpr int N = FR::N;
+  if (blockIdx.x == 0) {
+    uint32_t b = 0;
+    for (uint32_t s = threadIdx.x; s < nslices; s += 64) b |= bad_part[s];
+    const bool any_bad = __any((int)b) != 0;
+    if (threadIdx.x == 0) *gate = any_bad ? 0u : 1u;
+  }
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= l) return;
+  Fe<FR> acc = fe_zero<FR>();
+  for (uint32_t s = 0; s < nslices; s++) acc = fe_add<FR>(acc, fe_load<FR>(part + ((size_t)s * l + t) * N));
+  fe_store<FR>(neg_s + (size_t)t * N, fe_neg<FR>(acc));
+}
+
+// rho_c: one workgroup per commitment scans every cell's commit_index --
+// count * n_commits comparisons in all, no sort (a block's commitments are few
+// next to its cells; the scan of 8192 cells x 64 commitments is half a million
+// comparisons).  A commitment no cell names gets 0.
+template <class FR>
+__global__ __launch_bounds__(256) void k_cells_commit_weights(const uint32_t* __restrict__ r,
+                                                              const uint32_t* __restrict__ commit_index,
+                                                              uint32_t count, uint32_t* __restrict__ rho) {
+  constexpr int N = FR::N;
+  __shared__ uint32_t lds[4 * N];
+  const uint32_t c = blockIdx.x;
+  Fe<FR> acc = fe_zero<FR>();
+  for (uint32_t k = threadIdx.x; k < count; k += 256)
+    if (commit_index[k] == c) acc = fe_add<FR>(acc, fe_load<FR>(r + (size_t)k * N));
+  acc = wave_sum<FR>(acc);
+  if ((threadIdx.x & 63) == 0) fe_store<FR>(lds + (threadIdx.x >> 6) * N, acc);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; w++) acc = fe_add<FR>(acc, fe_load<FR>(lds + w * N));
+    fe_store<FR>(rho + (size_t)c * N, acc);
+  }
+}
+
+template <class FR>
+static int cells_scalars_impl(Ctx* ctx, const uint32_t* d_T, const uint32_t* d_r, const uint32_t* d_cell_index,
+                              const uint32_t* d_commit_index, size_t count, size_t n_commits, unsigned kl,
+                              unsigned kD, bool bitrev, uint32_t* d_out, uint32_t* d_gate, hipStream_t st) {
+  constexpr int N = FR::N;
+  const size_t l = (size_t)1 << kl;
+  const uint32_t nslices = (uint32_t)cells_fold_slices(count, kl);
+  uint32_t* rho = d_out;
+  uint32_t* s = rho + n_commits * N;
+  uint32_t* neg_s = s + count * N;
+  uint32_t* part = neg_s + l * N;
+  uint32_t* bad_part = part + (size_t)nslices * l * N;
+  if (n_commits)
+    hipLaunchKernelGGL(k_cells_commit_weights<FR>, dim3((unsigned)n_commits), dim3(256), 0, st, d_r, d_commit_index,
+                       (uint32_t)count, rho);
+  hipLaunchKernelGGL(k_cells_fold<FR>, dim3((unsigned)(l >> std::min(kl, 8u)), nslices), dim3(256), 0, st, d_T, d_r,
+                     d_cell_index, d_commit_index, (uint32_t)count, (uint32_t)n_commits, kl, kD, bitrev ? 1u : 0u,
+                     ctx->d_ntt_tw, (uint32_t)ctx->ntt_log2, s, part, bad_part);
+  hipLaunchKernelGGL(k_cells_total<FR>, dim3((unsigned)((l + 63) / 64)), dim3(64), 0, st, part, bad_part, nslices,
+                     (uint32_t)l, neg_s, d_gate);
+  KZGX_TRY_HIP(hipGetLastError());
+  return KZGX_OK;
+}
+
+// d_out: n_commits + count + l scalars, then cells_fold_slices(count, log2l) * l
+// scalars and as many words of scratch; the twiddle table of the size-D domain
+// must be built (ntt_twiddles) and st ordered behind it
+int cells_scalars(Ctx* ctx, const uint32_t* d_T, const uint32_t* d_r, const uint32_t* d_cell_index,
+                  const uint32_t* d_commit_index, size_t count, size_t n_commits, unsigned log2l, unsigned log2D,
+                  bool bitrev, uint32_t* d_out, uint32_t* d_gate, hipStream_t st) {
+  if (count == 0 || log2l > log2D || (int)log2D > ctx->ntt_log2) return KZGX_ERR_ARG;
+  ProfScope p(ctx, st, "cells_scalars");
+  return ctx->curve == KZGX_CURVE_BN254
+             ? cells_scalars_impl<BN254Fr>(ctx, d_T, d_r, d_cell_index, d_commit_index, count, n_commits, log2l,
+                                           log2D, bitrev, d_out, d_gate, st)
+             : cells_scalars_impl<BLS12381Fr>(ctx, d_T, d_r, d_cell_index, d_commit_index, count, n_commits, log2l,
+                                              log2D, bitrev, d_out, d_gate, st);
+}
+
 }  // namespace kzgx
 
 namespace kzgx {

@@ -41,6 +41,8 @@ EXPORTS = [
     "kzgx_g1_ntt", "kzgx_g1_ntt_device", "kzgx_prove_all_prepare", "kzgx_prove_all_batch",
     "kzgx_prove_all_batch_device",
     "kzgx_coset_points", "kzgx_prove_cosets_prepare", "kzgx_prove_cosets_batch", "kzgx_prove_cosets_batch_device",
+    "kzgx_verify_cells_aggregate", "kzgx_verify_cells_aggregate_device", "kzgx_verify_cells_aggregate_checked",
+    "kzgx_verify_cells_aggregate_checked_device",
 ]
 
 
@@ -67,6 +69,7 @@ PROVE_COSETS_EXTENDED = _header_define("KZGX_PROVE_COSETS_EXTENDED")
 _lib = None
 u64p = ctypes.POINTER(ctypes.c_uint64)
 intp = ctypes.POINTER(ctypes.c_int)
+u32p = ctypes.POINTER(ctypes.c_uint32)
 vp = ctypes.c_void_p
 sz = ctypes.c_size_t
 
@@ -192,6 +195,16 @@ def lib():
                                                        intp, u64p]),
             "kzgx_prove_cosets_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, ctypes.c_uint, sz, sz,
                                                               ctypes.c_int, vp, vp, vp, vp]),
+            "kzgx_verify_cells_aggregate": (ctypes.c_int, [vp, u64p, intp, sz, u32p, u32p, u64p, intp, u64p, u64p, sz,
+                                                           ctypes.c_uint, ctypes.c_uint, ctypes.c_int, intp]),
+            "kzgx_verify_cells_aggregate_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz,
+                                                                  ctypes.c_uint, ctypes.c_uint, ctypes.c_int, vp, vp]),
+            "kzgx_verify_cells_aggregate_checked": (ctypes.c_int, [vp, u64p, intp, sz, u32p, u32p, u64p, intp, u64p,
+                                                                   u64p, sz, ctypes.c_uint, ctypes.c_uint,
+                                                                   ctypes.c_int, ctypes.c_int, intp]),
+            "kzgx_verify_cells_aggregate_checked_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz,
+                                                                          ctypes.c_uint, ctypes.c_uint, ctypes.c_int,
+                                                                          ctypes.c_int, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -890,3 +903,65 @@ class Context:
         _chk(lib().kzgx_prove_cosets_batch_device(self.h, d_in, log2n, log2l, batch, stride,
                                                   _cosets_flags(extended, evals, bitrev), d_out, d_inf, d_y, stream),
              "kzgx_prove_cosets_batch_device")
+
+    # ---- aggregated cell verification ----
+    def _cells_host(self, fn, name, commits, commit_index, cell_index, proofs, ys, log2n, challenges, commit_inf,
+                    proof_inf, extended, bitrev, extra):
+        c = np.ascontiguousarray(commits, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        p = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        y = np.ascontiguousarray(ys, dtype=np.uint64)
+        assert y.ndim >= 2 and y.shape[-1] == 4
+        log2l = _log2_exact(y.shape[-2])
+        y = y.reshape(-1, y.shape[-2], 4)
+        nc, n = c.shape[0], p.shape[0]
+        ci = np.ascontiguousarray(commit_index, dtype=np.uint32).reshape(-1)
+        ki = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)
+        r = None if challenges is None or not n else as_scalars(challenges)
+        assert y.shape[0] == n and ci.shape[0] == n and ki.shape[0] == n and (r is None or r.shape[0] == n)
+        fc = None if commit_inf is None else np.ascontiguousarray(commit_inf, dtype=np.int32)
+        fp = None if proof_inf is None else np.ascontiguousarray(proof_inf, dtype=np.int32)
+        assert (fc is None or fc.shape[0] == nc) and (fp is None or fp.shape[0] == n)
+        ok = ctypes.c_int(0)
+        _chk(fn(self.h, _p(c) if nc else None, None if fc is None else fc.ctypes.data_as(intp), nc,
+                ci.ctypes.data_as(u32p) if n else None, ki.ctypes.data_as(u32p) if n else None,
+                _p(p) if n else None, None if fp is None else fp.ctypes.data_as(intp), _p(y) if n else None,
+                None if r is None else _p(r), n, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), *extra,
+                ctypes.byref(ok)), name)
+        return bool(ok.value)
+
+    def verify_cells_aggregate(self, commits, commit_index, cell_index, proofs, ys, log2n, challenges=None,
+                               commit_inf=None, proof_inf=None, extended=False, bitrev=False) -> bool:
+        """kzgx_verify_cells_aggregate: one pairing check of count coset openings.  commits (n_commits, 2 w64),
+        commit_index / cell_index (count,), proofs (count, 2 w64), ys (count, l, 4) with l = 2^log2l taken from
+        the shape; bitrev: cell_index is the chunk of the bit-reversed evaluation array and ys is in its order
+        (prove_cosets(..., bitrev=True) output as it comes); challenges None = library-drawn (r_0 = 1)."""
+        return self._cells_host(lib().kzgx_verify_cells_aggregate, "kzgx_verify_cells_aggregate", commits,
+                                commit_index, cell_index, proofs, ys, log2n, challenges, commit_inf, proof_inf,
+                                extended, bitrev, ())
+
+    def verify_cells_aggregate_checked(self, commits, commit_index, cell_index, proofs, ys, log2n, challenges=None,
+                                       commit_inf=None, proof_inf=None, extended=False, bitrev=False,
+                                       subgroup: bool = False) -> bool:
+        """verify_cells_aggregate behind the G1 check of every commit and proof (False if one fails)."""
+        return self._cells_host(lib().kzgx_verify_cells_aggregate_checked, "kzgx_verify_cells_aggregate_checked",
+                                commits, commit_index, cell_index, proofs, ys, log2n, challenges, commit_inf,
+                                proof_inf, extended, bitrev, (int(bool(subgroup)),))
+
+    def verify_cells_aggregate_device(self, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index,
+                                      d_proofs, d_proof_inf, d_ys, d_challenges, count, log2n, log2l, d_ok,
+                                      extended=False, bitrev=False, stream=None):
+        """kzgx_verify_cells_aggregate_device: device pointers (uint32 indices and flags), d_ok one uint32,
+        enqueued on stream."""
+        _chk(lib().kzgx_verify_cells_aggregate_device(
+            self.h, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index, d_proofs, d_proof_inf, d_ys,
+            d_challenges, count, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), d_ok, stream),
+            "kzgx_verify_cells_aggregate_device")
+
+    def verify_cells_aggregate_checked_device(self, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index,
+                                              d_proofs, d_proof_inf, d_ys, d_challenges, count, log2n, log2l,
+                                              subgroup, d_ok, extended=False, bitrev=False, stream=None):
+        """kzgx_verify_cells_aggregate_checked_device: the same behind the G1 check, still asynchronous."""
+        _chk(lib().kzgx_verify_cells_aggregate_checked_device(
+            self.h, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index, d_proofs, d_proof_inf, d_ys,
+            d_challenges, count, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), int(bool(subgroup)), d_ok,
+            stream), "kzgx_verify_cells_aggregate_checked_device")

@@ -320,7 +320,11 @@ class trusted_setup {
    *  257.8 GB of HBM, c = 16 137.5 GB, c = 12 11.8 GB, and BLS12-381 c = 16
    *  240.6 GB.  Commits and proofs over that prefix then run as plain table
    *  sums.  window_bits = 0 drops the table.  Without it, batches run on
-   *  the default table below. */
+   *  the default table below.  These byte counts are the footprint: for
+   *  1024 .. 16384 points the library splits it between a block table of
+   *  cross-point subset sums, which serves batches of >= 64 commits or
+   *  proofs, and a narrower window table for single calls (BN254 c = 17:
+   *  176.1 + 73.0 GB; kzgx_set_fixed_joint in kzg_gpu.h turns that off). */
   void precompute(int window_bits = 16, size_t points = 0);
   /** Extension: the default table (kzgx_set_default_table), built with
    *  every setup: odd multiples of the first 4097 SRS points at the widest

@@ -153,8 +153,32 @@ int kzgx_shared_tables(int device, size_t* count, size_t* bytes);
 int kzgx_release_cached_memory(int device);
 /* layout of the built table: *point_major = 1 (M[i][w][j]) or 0 (M[w][i][j]) */
 int kzgx_fixed_base_layout(const kzgx_ctx* ctx, int* point_major);
-/* built table: window bits (0 = none), points covered, device bytes */
+/* built table: the window bits asked for (0 = none), points covered, device
+ * bytes of everything built for them (the window and the block table) */
 int kzgx_fixed_base_info(const kzgx_ctx* ctx, int* c, size_t* n_points, size_t* bytes);
+/* The block table (extension, no reference counterpart).
+ * kzgx_set_fixed_base(c, n) means "the fastest fixed-base tables inside
+ * kzgx_fixed_base_bytes(c, n)": from 1024 tabled points on it builds a table
+ * of the signed subset sums of blocks of g consecutive SRS points (2^(g-1)
+ * entries per block, the widest g <= 25 that leaves room) beside a window
+ * table at the widest c' <= c that fits the rest -- BN254 c = 17 over 4097
+ * points: g = 25 (176.1 GB) + c' = 15 (73.0 GB).  Batches of >= 64 MSMs with
+ * n <= n_points then cost ceil(n / g) bits(r) mixed additions per MSM and one
+ * shared pass of bits(r) doublings instead of n ceil(bits(r) / c); single
+ * calls, batches below 64 and XYZZ partial records stay on the window table.
+ * g = -1: that automatic choice (the default, or $KZGX_FIXED_JOINT read at
+ * kzgx_create); 0: no block table, the window table at c alone; 2..25: that
+ * block size at any n_points, serving every batch >= 1 (tests), KZGX_ERR_ARG
+ * if it does not fit the footprint.  Rebuilds at once when a table is set. */
+int kzgx_set_fixed_joint(kzgx_ctx* ctx, int g);
+/* built block table: block size (0 = none), blocks, device bytes */
+int kzgx_fixed_joint_info(const kzgx_ctx* ctx, int* g, size_t* blocks, size_t* bytes);
+/* built window table: its own window bits (<= the request) and device bytes */
+int kzgx_fixed_window_info(const kzgx_ctx* ctx, int* c, size_t* bytes);
+/* block ranges per MSM of the block table's accumulation (each lane sums
+ * blocks / ranges entries and the Horner pass folds ranges times the
+ * partials; 0 = automatic: 1; <= 8; $KZGX_FIXED_JOINT_RANGES at kzgx_create) */
+int kzgx_set_fixed_joint_ranges(kzgx_ctx* ctx, unsigned ranges);
 /* device bytes a table of window c over n_points would take (no context) */
 int kzgx_fixed_base_bytes(int curve, int c, size_t n_points, size_t* bytes);
 /* bounded-memory precompute: the widest supported window c <= 17 whose
@@ -168,7 +192,8 @@ int kzgx_fixed_base_bytes(int curve, int c, size_t n_points, size_t* bytes);
 int kzgx_set_fixed_base_budget(kzgx_ctx* ctx, size_t budget_bytes, size_t n_points, int* c_out);
 /* SRS points summed per accumulation thread on the fixed-base path
  * (0 = automatic, the default: 16 for batches of >= 64 MSMs, else enough
- * threads to fill the GPU, with a wavefront-level fold for single MSMs) */
+ * threads to fill the GPU, with a wavefront-level fold for single MSMs).
+ * Ignored by calls the block table serves: their lanes are bit planes. */
 int kzgx_set_fixed_points_per_thread(kzgx_ctx* ctx, unsigned p);
 /* measurement: mixed additions per second of the MSM accumulation loop
  * (the XYZZ mixed add k_fixed_accum inlines, same waves per SIMD) on

@@ -519,7 +519,7 @@ int kzgx_init_device(int curve, int device) {
       kzgx::warm_srs,        kzgx::warm_pairing,    kzgx::warm_verify_wave, kzgx::warm_latency,
       kzgx::warm_fixed_bn_a, kzgx::warm_fixed_bn_b, kzgx::warm_fixed_bn_c,  kzgx::warm_fixed_bn_d,
       kzgx::warm_fixed_bls_a, kzgx::warm_fixed_bls_b, kzgx::warm_fixed_bls_c, kzgx::warm_fixed_bls_d,
-      kzgx::warm_subgroup};
+      kzgx::warm_subgroup,   kzgx::warm_msm_joint};
   for (auto f : warm) KZGX_TRY(f(st));
   // the generator comb tables (per process, per device and curve)
   kzgx::GenTables g;
@@ -545,6 +545,17 @@ int kzgx_create(kzgx_ctx** out, int curve, int device) {
     if (kzgx::window_bits_supported(c)) ctx->c.c = c;
   }
   ctx->c.W = (257 + ctx->c.c - 1) / ctx->c.c;
+  // the block table beside the main fixed-base table: automatic unless
+  // $KZGX_FIXED_JOINT says otherwise (0 = off: the window table alone)
+  ctx->c.fixed.joint.g_req = -1;
+  if (const char* e = getenv("KZGX_FIXED_JOINT")) {
+    const int g = atoi(e);
+    if (g == -1 || g == 0 || (g >= 2 && g <= 25)) ctx->c.fixed.joint.g_req = g;
+  }
+  if (const char* e = getenv("KZGX_FIXED_JOINT_RANGES")) {  // kzgx_set_fixed_joint_ranges' default, for A/B runs
+    const int r = atoi(e);
+    if (r >= 0 && r <= 8) ctx->c.fixed.joint.ranges = (uint32_t)r;
+  }
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = stream_take(device, &ctx->c.stream);
   if (e != hipSuccess) {
@@ -601,7 +612,7 @@ void kzgx_destroy(kzgx_ctx* ctx) {
     void* wb[] = {w.counts, w.offsets, w.cursors, w.entries, w.bsum,  w.heads,
                   w.tails,  w.tailk,   w.rt,      w.q,       w.parts, w.fpart, w.fsum, w.gpart, w.gmeta, w.sstate, w.qbig,
                   w.lat_cnt, w.var_tab, w.var_parts, w.var_scal, w.var_pt, w.var_inf, w.ntt_tmp, w.ntt_coef,
-                  w.g1n_rec, w.fk_c, w.fkm_y};
+                  w.g1n_rec, w.fk_c, w.fkm_y, w.jidx};
     for (void* p : wb)
       if (p) (void)hipFree(p);
     if (w.done) (void)hipEventDestroy(w.done);
@@ -742,8 +753,44 @@ int kzgx_fixed_base_layout(const kzgx_ctx* ctx, int* point_major) {
 
 int kzgx_fixed_base_info(const kzgx_ctx* ctx, int* c, size_t* n_points, size_t* bytes) {
   if (!ctx) return KZGX_ERR_ARG;
-  if (c) *c = ctx->c.fixed.c;
+  if (c) *c = ctx->c.fixed.c ? ctx->c.fixed.c_req : 0;  // the request; the window table itself may be narrower
   if (n_points) *n_points = ctx->c.fixed.n_t;
+  if (bytes) *bytes = ctx->c.fixed.bytes + ctx->c.fixed.joint.bytes;
+  return KZGX_OK;
+}
+
+int kzgx_set_fixed_joint(kzgx_ctx* ctx, int g) {
+  KZGX_TRY(activate(ctx));
+  if (g != -1 && g != 0 && (g < 2 || g > 25)) return KZGX_ERR_ARG;
+  KZGX_TRY_HIP(hipStreamSynchronize(ctx->c.stream));
+  const int keep = ctx->c.fixed.joint.g_req;
+  ctx->c.fixed.joint.g_req = g;
+  if (ctx->c.fixed.c_req != 0 && ctx->c.n_srs != 0) {
+    const int rc = kzgx::fixed_build_table(&ctx->c, ctx->c.fixed, ctx->d_srs_canon, ctx->c.n_srs);
+    if (rc == KZGX_ERR_ARG) ctx->c.fixed.joint.g_req = keep;  // no split fits: the tables stay as they were
+    return rc;
+  }
+  return KZGX_OK;
+}
+
+int kzgx_set_fixed_joint_ranges(kzgx_ctx* ctx, unsigned ranges) {
+  KZGX_TRY(activate(ctx));
+  if (ranges > 8) return KZGX_ERR_ARG;  // 0 = automatic
+  ctx->c.fixed.joint.ranges = ranges;
+  return KZGX_OK;
+}
+
+int kzgx_fixed_joint_info(const kzgx_ctx* ctx, int* g, size_t* blocks, size_t* bytes) {
+  if (!ctx) return KZGX_ERR_ARG;
+  if (g) *g = ctx->c.fixed.joint.g;
+  if (blocks) *blocks = ctx->c.fixed.joint.blocks;
+  if (bytes) *bytes = ctx->c.fixed.joint.bytes;
+  return KZGX_OK;
+}
+
+int kzgx_fixed_window_info(const kzgx_ctx* ctx, int* c, size_t* bytes) {
+  if (!ctx) return KZGX_ERR_ARG;
+  if (c) *c = ctx->c.fixed.c;
   if (bytes) *bytes = ctx->c.fixed.bytes;
   return KZGX_OK;
 }

@@ -56,6 +56,8 @@ struct MsmWs {
   uint8_t* var_inf = nullptr;
   size_t var_tab_b = 0, var_parts_b = 0, var_scal_b = 0, var_pt_b = 0, var_inf_b = 0;
   uint32_t* lat_cnt = nullptr;  // [64] arrival counters of the one-launch latency path (msm_fixed.hip)
+  uint32_t* jidx = nullptr;     // the block table path's (MSM, block, plane) index words (msm_joint.hip)
+  size_t jidx_b = 0;
   // evaluation form (ntt.hip, kzgx_api.hip): the two-pass transform's intermediate,
   // and the coefficients handed on to the MSM / the opening pipeline
   uint32_t *ntt_tmp = nullptr, *ntt_coef = nullptr;
@@ -120,6 +122,20 @@ struct FkSetup {
   hipEvent_t ev = nullptr;
 };
 
+// signed subset sums of blocks of g consecutive SRS points (msm_joint.hip):
+// entry j < 2^(g_b - 1) of block b = P_top + sum_i (2 j_i - 1) P_i, packed
+// affine (x = y = 0: infinity), block stride 2^(g - 1) entries
+struct JointTable {
+  int g_req = 0;        // -1 automatic, 0 off, 2..25 forced (kzgx_set_fixed_joint)
+  uint32_t ranges = 0;  // block ranges per MSM of the accumulation, 0 = automatic
+  int g = 0;            // built table
+  uint32_t blocks = 0;
+  size_t n_t = 0;
+  uint32_t* d = nullptr;
+  size_t bytes = 0;
+  uint64_t n_inf = 0;  // entries at infinity (0: the accumulation tests none)
+};
+
 // precomputed odd multiples of the SRS prefix (msm_fixed.hip, indexed by
 // the regular odd digits of fixed_accum.hpp):
 // M[w][i][j] = (2 j + 1) 2^(c w) P_i, packed affine, w < W, i < n_t, j < 2^(c-1)
@@ -137,6 +153,9 @@ struct FixedTable {
   bool any_inf = true;     // some flag of inf is set (else the kernels get no flags)
   uint32_t fin0 = UINT32_MAX;  // first finite point of the prefix (k_fixed_accum's identity terms)
   int shared = 0;  // registry id of a shared default table (kzgx_api.hip), 0 = owned by this context
+  // the block table built beside it inside the same footprint (the main
+  // table only; serves the batched calls, msm_joint.hip)
+  JointTable joint;
 };
 
 // per-device table memory (kzgx_api.hip): the cached block of the last freed
@@ -334,6 +353,16 @@ int fixed_msm_table(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t 
                     uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st, uint32_t* xyzz_out);
 int fixed_msm(Ctx* ctx, const uint32_t* d_scalars, size_t n, size_t batch, size_t stride_words, uint32_t* d_out,
               uint32_t* d_out_inf, hipStream_t st, uint32_t* xyzz_out);
+// the block table (msm_joint.hip): bytes of one at block size g over n
+// points; the (g, window bits) split of set_fixed_base(c, n)'s footprint;
+// build / free; whether it serves a call, and the call
+size_t joint_table_bytes(int curve, int g, size_t n);
+int joint_plan(int curve, int c, size_t n, int g_req, int* g, int* c_win);
+int joint_build(Ctx* ctx, JointTable& jt, const uint32_t* d_canon, size_t n, int g);
+void joint_free(JointTable& jt);
+bool joint_serves(const FixedTable& ft, size_t n, size_t batch, bool xyzz_out);
+int joint_msm(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n, size_t batch, size_t stride_words,
+              uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st);
 int srs_upload(Ctx* ctx, const uint32_t* d_canon, size_t n);
 // mixed additions / s of the fixed-base accumulation loop on L1-resident operands (msm_fixed.hip)
 int microbench_mixed_add(Ctx* ctx, double* rate);

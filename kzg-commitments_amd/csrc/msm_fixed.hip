@@ -165,14 +165,17 @@ static bool fixed_point_major(int c, int layout_req) {
 
 template <class C>
 static int fixed_build_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_canon, size_t n) {
-  const int c = ft.c_req;
+  // the request's footprint, fixed_table_bytes(c_req, n), holds the block
+  // table (msm_joint.hip; g = 0: none) and a window table at c <= c_req
+  int g = 0, c = ft.c_req;
+  KZGX_TRY(joint_plan(ctx->curve, ft.c_req, n, ft.joint.g_req, &g, &c));
   const int W = fixed_windows(ctx->curve, c);
   const uint64_t H = 1ull << (c - 1);
   const size_t PB = packed_words<C>() * sizeof(uint32_t);
   const size_t bytes = (size_t)W * n * H * PB;
-  // drop the old table (and its infinity flags) first: the new one may need
+  // drop the old tables (and the infinity flags) first: the new ones may need
   // most of the device
-  if (ft.d || ft.inf) {
+  if (ft.d || ft.inf || ft.joint.d) {
     KZGX_TRY_HIP(hipDeviceSynchronize());
     fixed_free_table(ft);
   }
@@ -189,13 +192,14 @@ static int fixed_build_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_canon, s
         fixed_free_table(ft);
       }
     }
-  } g{ft};
+  } gd{ft};
+  if (g) KZGX_TRY(joint_build(ctx, ft.joint, d_canon, n, g));
   KZGX_TRY_HIP(table_malloc((void**)&ft.d, bytes));
   ft.bytes = bytes;
-  KZGX_TRY_HIP(hipMalloc((void**)&g.bases, (size_t)W * n * PB));
-  KZGX_TRY_HIP(hipMalloc((void**)&g.inf, n));
-  uint32_t* d_bases = g.bases;
-  uint8_t* d_inf = g.inf;
+  KZGX_TRY_HIP(hipMalloc((void**)&gd.bases, (size_t)W * n * PB));
+  KZGX_TRY_HIP(hipMalloc((void**)&gd.inf, n));
+  uint32_t* d_bases = gd.bases;
+  uint8_t* d_inf = gd.inf;
   hipStream_t st = ctx->stream;
   if (ctx->d_table && ctx->c == c && W <= ctx->W && n <= ctx->n_srs)
     hipLaunchKernelGGL(k_fixed_bases_from_table<C>, dim3((unsigned)(((uint64_t)W * n + 255) / 256)), dim3(256), 0, st,
@@ -203,7 +207,7 @@ static int fixed_build_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_canon, s
   else
     hipLaunchKernelGGL(k_fixed_bases<C>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, d_canon, (uint32_t)n, W, c,
                        d_bases, d_inf);
-  ft.point_major = fixed_point_major(c, ft.layout_req);
+  ft.point_major = fixed_point_major(ft.c_req, ft.layout_req);  // by the request, whatever the split
   const TabStrides ts = fixed_strides<C>(ft.point_major, W, n, H);
   // the batch-affine builder (setup.hip): one inversion per 16 entries
   {
@@ -221,7 +225,7 @@ static int fixed_build_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_canon, s
     const auto f = std::find(h.begin(), h.end(), (uint8_t)0);
     ft.fin0 = f == h.end() ? UINT32_MAX : (uint32_t)(f - h.begin());
   }
-  g.ok = true;
+  gd.ok = true;
   ft.inf = d_inf;
   ft.c = c;
   ft.W = W;
@@ -300,6 +304,7 @@ void fixed_free_table(FixedTable& ft) {
     if (ft.d) table_free(ft.d, ft.bytes);
     if (ft.inf) (void)hipFree(ft.inf);
   }
+  joint_free(ft.joint);  // the request (g_req, ranges) stays
   ft.d = nullptr;
   ft.inf = nullptr;
   ft.bytes = 0;
@@ -350,6 +355,10 @@ bool fixed_usable(const Ctx* ctx, size_t n) { return fixed_table_usable(ctx->fix
 
 int fixed_msm_table(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n, size_t batch, size_t stride_words,
                     uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st, uint32_t* xyzz_out) {
+  // batched calls take the block table when there is one; the window table
+  // keeps the latency kernel, the XYZZ partial records and the flat path
+  if (joint_serves(ft, n, batch, xyzz_out != nullptr))
+    return joint_msm(ctx, ft, d_scalars, n, batch, stride_words, d_out, d_out_inf, st);
   return ctx->curve == KZGX_CURVE_BN254
              ? fixed_msm_c<BN254G1>(ctx, ft, d_scalars, n, batch, stride_words, d_out, d_out_inf, st, xyzz_out)
              : fixed_msm_c<BLS12381G1>(ctx, ft, d_scalars, n, batch, stride_words, d_out, d_out_inf, st, xyzz_out);

@@ -24,6 +24,7 @@ EXPORTS = [
     "kzgx_srs_size", "kzgx_stream", "kzgx_prof_enable", "kzgx_prof_read", "kzgx_prof_clear", "kzgx_set_window_bits", "kzgx_set_segment",
     "kzgx_set_fixed_base", "kzgx_fixed_base_info", "kzgx_fixed_base_bytes", "kzgx_set_fixed_base_budget",
     "kzgx_set_fixed_base_layout", "kzgx_fixed_base_layout", "kzgx_set_default_table", "kzgx_default_table_info",
+    "kzgx_set_fixed_joint", "kzgx_fixed_joint_info", "kzgx_fixed_window_info", "kzgx_set_fixed_joint_ranges",
     "kzgx_microbench_mad_u64", "kzgx_microbench_mad_u64_clock", "kzgx_clock_probe", "kzgx_set_fixed_points_per_thread", "kzgx_set_small_batch", "kzgx_microbench_mixed_add", "kzgx_load_srs_g1", "kzgx_gen_srs_g1", "kzgx_get_srs_g1", "kzgx_msm_g1",
     "kzgx_msm_g1_batch", "kzgx_msm_g1_batch_device", "kzgx_quotient_single_batch_device",
     "kzgx_prove_single_batch", "kzgx_prove_single_batch_device", "kzgx_prove_range", "kzgx_poly_eval",
@@ -115,6 +116,10 @@ def lib():
             "kzgx_fixed_base_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, sz, ctypes.POINTER(sz)]),
             "kzgx_set_fixed_base_budget": (ctypes.c_int, [vp, sz, sz, intp]),
             "kzgx_set_fixed_base_layout": (ctypes.c_int, [vp, ctypes.c_int]),
+            "kzgx_set_fixed_joint": (ctypes.c_int, [vp, ctypes.c_int]),
+            "kzgx_fixed_joint_info": (ctypes.c_int, [vp, intp, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+            "kzgx_fixed_window_info": (ctypes.c_int, [vp, intp, ctypes.POINTER(sz)]),
+            "kzgx_set_fixed_joint_ranges": (ctypes.c_int, [vp, ctypes.c_uint]),
             "kzgx_set_default_table": (ctypes.c_int, [vp, ctypes.c_int, sz]),
             "kzgx_default_table_info": (ctypes.c_int, [vp, intp, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
             "kzgx_fixed_base_layout": (ctypes.c_int, [vp, intp]),
@@ -392,6 +397,31 @@ class Context:
         _chk(lib().kzgx_fixed_base_info(self.h, ctypes.byref(c), ctypes.byref(n), ctypes.byref(b)),
              "kzgx_fixed_base_info")
         return c.value, n.value, b.value
+
+    def set_fixed_joint(self, g: int):
+        """the block table beside the fixed-base table: -1 automatic, 0 off,
+        2..25 that block size at any size and batch (rebuilds a set table)"""
+        _chk(lib().kzgx_set_fixed_joint(self.h, g), "kzgx_set_fixed_joint")
+
+    def set_fixed_joint_ranges(self, ranges: int):
+        """block ranges per MSM of the block table's accumulation (0 = automatic)"""
+        _chk(lib().kzgx_set_fixed_joint_ranges(self.h, ranges), "kzgx_set_fixed_joint_ranges")
+
+    def fixed_joint_info(self):
+        """(block size g, blocks, device bytes) of the built block table, g = 0: none"""
+        g = ctypes.c_int(0)
+        n = sz(0)
+        b = sz(0)
+        _chk(lib().kzgx_fixed_joint_info(self.h, ctypes.byref(g), ctypes.byref(n), ctypes.byref(b)),
+             "kzgx_fixed_joint_info")
+        return g.value, n.value, b.value
+
+    def fixed_window_info(self):
+        """(window bits, device bytes) of the built window table itself"""
+        c = ctypes.c_int(0)
+        b = sz(0)
+        _chk(lib().kzgx_fixed_window_info(self.h, ctypes.byref(c), ctypes.byref(b)), "kzgx_fixed_window_info")
+        return c.value, b.value
 
     def set_fixed_base_budget(self, budget_bytes: int, n_points: int) -> int:
         """widest table window whose table fits budget_bytes and free device

@@ -175,6 +175,8 @@ class trusted_setup {
                         const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
                         const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended, bool bit_reversed,
                         bool checked, bool check_subgroup);
+  std::vector<Fr> recovered(const std::vector<uint32_t>& cell_index, const std::vector<std::vector<Fr>>& values,
+                            unsigned log2n, bool bit_reversed, std::vector<proof>* proofs);
 
  public:
   /** random tau (std::random_device), [tau^i]G1 and [tau^i]G2 for
@@ -300,6 +302,30 @@ class trusted_setup {
                            const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
                            const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
                            bool bit_reversed, bool check_subgroup);
+  /** Extension: rebuild one erasure-coded blob from at least half of its cells
+   *  (kzgx_recover_cells): the cells are those of create_coset_proofs(p, log2n,
+   *  log2l, extended = true, bit_reversed), cell_index[k] the element number and
+   *  values[k] its 2^log2l values in the coset's point order (log2l is taken
+   *  from the values' length).  Returns all 2^(log2n + 1) values in
+   *  kzgx_prove_cosets_batch's y layout for the same order: cell i is elements
+   *  i 2^log2l .. (i + 1) 2^log2l - 1.  Needs no setup points.
+   *  @throws std::invalid_argument on mismatched sizes, values whose length is
+   *          not one power of two shared by all cells, an index out of range, a
+   *          cell given twice, fewer than half the cells, log2l > log2n, more
+   *          than 2^KZGX_RECOVER_MAX_LOG2_CELLS cells, or a domain beyond the
+   *          curve's
+   *  @throws std::domain_error if no polynomial of fewer than 2^log2n
+   *          coefficients takes every given value (only detectable with more
+   *          than half the cells) */
+  std::vector<Fr> recover_cells(const std::vector<uint32_t>& cell_index, const std::vector<std::vector<Fr>>& values,
+                                unsigned log2n, bool bit_reversed = false);
+  /** Extension: the same with every cell's proof recomputed
+   *  (kzgx_recover_cells_and_proofs): the values and create_coset_proofs'
+   *  output for the recovered polynomial.
+   *  @throws as recover_cells and create_coset_proofs */
+  std::pair<std::vector<Fr>, std::vector<proof>> recover_cells_and_proofs(
+      const std::vector<uint32_t>& cell_index, const std::vector<std::vector<Fr>>& values, unsigned log2n,
+      bool bit_reversed = false);
   /** Extension: every installed G1 and G2 point is canonical, on its curve
    *  and (subgroup) in the prime-order subgroup (kzgx_srs_check, on the
    *  device).  trusted_setup(filename) tests on-curve only: call this after

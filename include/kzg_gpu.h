@@ -727,6 +727,92 @@ int kzgx_verify_cells_aggregate_checked_device(kzgx_ctx* ctx, const void* d_comm
                                                size_t count, unsigned log2n, unsigned log2l, int flags, int subgroup,
                                                void* d_ok, void* stream);
 
+/* ---- cell recovery (extension) -----------------------------------------------------------
+ * Rebuilds erasure-coded blobs from any half of their cells: the inverse of
+ * kzgx_prove_cosets_batch(..., KZGX_PROVE_COSETS_EXTENDED), whose size-2n domain
+ * carries a polynomial of n coefficients at rate 1/2.  Notation as above: n =
+ * 2^log2n, l = 2^log2l, D = 2n, R = D / l cosets ("cells"), w = kzgx_domain_root(
+ * curve, log2 D), w_R = w^l, coset i = {w^(i + R j), j < l} = the roots of X^l -
+ * w_R^i.  Per blob, with M the cosets it has no cell of (|M| <= R / 2):
+ *   Z(X) = Zs(X^l), Zs(Y) = prod_{i in M} (Y - w_R^i)        -- constant on a coset;
+ *   E[e] = y[e] Zs(w_R^(e mod R)) on received cosets, 0 on the others: the values of
+ *    P Z on the domain, deg(P Z) < n + |M| l <= D, so Q = INTT_D(E) exactly;
+ *   P(g w^e) = NTT_D(g^j Q[j])[e] / Zs(g^l w_R^(e mod R)) for the field's NTT
+ *    generator g (BLS12-381: 7, BN254: 2; g^l w_R^p = w_R^i would need g^D = 1, so no
+ *    divisor is zero); P's coefficients = g^(-j) INTT_D of that, truncated to n;
+ *   out_y = NTT_D of the zero-extended coefficients.
+ * Four size-D transforms (kzgx_ntt's kernels) and six small Fr kernels per chunk; the
+ * locator costs R |M| products and R inversions per blob, and no coefficient of Z is
+ * ever formed.  No interpolation over arbitrary points.  No reference counterpart.
+ *  cells: a flat list exactly as kzgx_verify_cells_aggregate takes it: cell k belongs
+ *   to blob blob_index[k] < n_blobs, is cell cell_index[k] < R and has l values at
+ *   ys + k l.  Any order; the cells of different blobs may interleave; blobs may have
+ *   different erasure patterns and different counts (>= R / 2 each).  The inputs are
+ *   only read.
+ *  flags: KZGX_PROVE_COSETS_EXTENDED must be set (without it the domain has no
+ *   redundancy), so one flag word serves prove, verify and recover.  KZGX_NTT_BITREV
+ *   as in the other two cell calls: cell_index is then the chunk number p of the
+ *   bit-reversed evaluation array and the l values come in bit-reversed order.
+ *  out_y: n_blobs x D scalars in exactly the layout of kzgx_prove_cosets_batch's y for
+ *   the same flags; out_coeffs: n_blobs x n.  Either may be NULL, not both in the
+ *   plain forms.  The _and_proofs forms add the n_blobs x R proofs of
+ *   kzgx_prove_cosets_batch in its order: the recovered coefficients go to
+ *   kzgx_prove_cosets_batch_device as they lie on the device, so these forms need the
+ *   G1 SRS and share that call's cached setup; the plain forms need no SRS at all.
+ *  ok[b] = 1 iff a polynomial of degree < n takes every value supplied for blob b: the
+ *   recovered values are compared with all of them, an exact test, not a random one.
+ *   With exactly R / 2 cells every input is consistent (any n values on n points
+ *   interpolate), so ok is always 1 there and a corrupted value goes unnoticed; from
+ *   R / 2 + 1 cells on a single wrong value gives ok = 0.  A blob with ok = 0 gets
+ *   all-zero out_y and out_coeffs, and its proofs are the zero polynomial's: infinity.
+ *  Device entries: device pointers (indices and ok uint32), asynchronous on stream
+ *   (NULL = the context's), no host read-back, nothing read out of bounds.  A blob with
+ *   fewer than R / 2 distinct cells, a duplicate (blob, cell) or a cell_index >= R gets
+ *   ok = 0; a blob_index >= n_blobs forces ok = 0 for every blob of the call.
+ *  Batching: chunks of max(1, KZGX_RECOVER_CHUNK_SCALARS / D) blobs, so the workspace
+ *   is bounded per stream by max(KZGX_RECOVER_CHUNK_SCALARS, D) scalars for the
+ *   transforms in place, as many for a two-pass transform's intermediate, half as
+ *   many for the coefficients, and 2 R scalars + R + 4 words per blob of the chunk for
+ *   the locator and the cell map.  Each chunk reads the whole index list once.
+ *  When it pays (BLS12-381, MI355X, profiles/recover_cells.json, DESIGN.md "Cell
+ *   recovery"): at (12, 6), bit-reversed, 64 random cells of 128 per blob, a device call is
+ *   latency-bound at about 1 ms per chunk -- 1 blob 1.02 ms, 8 blobs 1.03 ms, 64 blobs
+ *   1.10 ms (58k blobs/s) -- against 0.48 to 0.51 ms for its four transforms alone
+ *   (kzgx_ntt_device, same run): x2.1 to x2.2 of that floor, and the locator is the
+ *   difference (0.49 ms at every size: one lane per (blob, p) runs |M| dependent products
+ *   and a Fermat inverse; a wave-level batch inversion is not built).  The shift passes
+ *   are 0.02 to 0.03 ms each.  With the proofs the call costs what
+ *   kzgx_prove_cosets_batch_device costs plus 0.7 to 0.8 ms (74.4 against 73.6 ms for 1
+ *   blob, 159.3 against 158.5 ms for 64): x1.005 to x1.010.  The route that existed
+ *   before, kzgx_poly_interpolate of a blob's 4096 received points (host pointers, one
+ *   blob per call), took 1.41 ms of host wall clock for one blob: a single blob is about
+ *   LEVEL with it, and the recovery wins only with the batch (one call for any number of
+ *   blobs) or when the values of the missing cells, the consistency answer or device
+ *   pointers are wanted.  No path is chosen silently.
+ *  Statuses: log2l > log2n, log2n + 1 > kzgx_ntt_max_log2(curve), R >
+ *   2^KZGX_RECOVER_MAX_LOG2_CELLS, KZGX_PROVE_COSETS_EXTENDED missing or an unknown
+ *   flag, a NULL required pointer, and on the host entries an index out of range, a
+ *   duplicate (blob, cell) or a blob with fewer than R / 2 cells: KZGX_ERR_ARG; the
+ *   _and_proofs forms: no SRS: KZGX_ERR_NO_SRS, 2^log2n larger than the installed SRS:
+ *   KZGX_ERR_DEGREE; n_blobs == 0: KZGX_OK. */
+#define KZGX_RECOVER_MAX_LOG2_CELLS 12 /* R <= 4096: the locator costs R |M| products per blob */
+#define KZGX_RECOVER_CHUNK_SCALARS 1048576
+int kzgx_recover_cells(kzgx_ctx* ctx, const uint32_t* blob_index, const uint32_t* cell_index, const uint64_t* ys,
+                       size_t count, size_t n_blobs, unsigned log2n, unsigned log2l, int flags, uint64_t* out_y,
+                       uint64_t* out_coeffs, int* ok);
+int kzgx_recover_cells_device(kzgx_ctx* ctx, const void* d_blob_index, const void* d_cell_index, const void* d_ys,
+                              size_t count, size_t n_blobs, unsigned log2n, unsigned log2l, int flags,
+                              void* d_out_y, void* d_out_coeffs, void* d_ok, void* stream);
+int kzgx_recover_cells_and_proofs(kzgx_ctx* ctx, const uint32_t* blob_index, const uint32_t* cell_index,
+                                  const uint64_t* ys, size_t count, size_t n_blobs, unsigned log2n, unsigned log2l,
+                                  int flags, uint64_t* out_y, uint64_t* out_coeffs, uint64_t* out_proofs_xy,
+                                  int* out_proofs_is_inf, int* ok);
+int kzgx_recover_cells_and_proofs_device(kzgx_ctx* ctx, const void* d_blob_index, const void* d_cell_index,
+                                         const void* d_ys, size_t count, size_t n_blobs, unsigned log2n,
+                                         unsigned log2l, int flags, void* d_out_y, void* d_out_coeffs,
+                                         void* d_out_proofs_xy, void* d_out_proofs_is_inf, void* d_ok,
+                                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

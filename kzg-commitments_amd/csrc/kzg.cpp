@@ -945,6 +945,70 @@ bool trusted_setup::coset_aggregated(std::vector<commit>& commits, const std::ve
   return ok != 0;
 }
 
+// one blob through kzgx_recover_cells(_and_proofs): the D values, and the R proofs when asked for
+std::vector<Fr> trusted_setup::recovered(const std::vector<uint32_t>& cell_index,
+                                         const std::vector<std::vector<Fr>>& values, unsigned log2n,
+                                         bool bit_reversed, std::vector<proof>* proofs) {
+  const size_t m = cell_index.size();
+  if (values.size() != m) throw std::invalid_argument("recover_cells: size mismatch");
+  if (m == 0) throw std::invalid_argument("recover_cells: no cells");
+  const size_t l = values[0].size();
+  if (l == 0 || (l & (l - 1))) throw std::invalid_argument("recover_cells: a cell's size is not a power of two");
+  unsigned kl = 0;
+  while (((size_t)1 << kl) < l) kl++;
+  if (kl > log2n) throw std::invalid_argument("recover_cells: a coset larger than the domain");
+  if (log2n > 31 || (int)log2n + 1 > kzgx_ntt_max_log2(g_curve))
+    throw std::invalid_argument("recover_cells: the extended domain exceeds the curve's power-of-two domain");
+  if (log2n + 1 - kl > KZGX_RECOVER_MAX_LOG2_CELLS) throw std::invalid_argument("recover_cells: too many cells");
+  const size_t D = (size_t)2 << log2n, R = D >> kl;
+  if (proofs && D / 2 >= n) throw std::invalid_argument("the domain must be smaller than the setup size (num_coeffs)");
+  if (m < R / 2) throw std::invalid_argument("recover_cells: fewer than half the cells");
+  std::vector<bool> seen(R, false);
+  std::vector<uint64_t> y(4 * m * l), out(4 * D);
+  for (size_t k = 0; k < m; k++) {
+    if (values[k].size() != l) throw std::invalid_argument("recover_cells: cells of different sizes");
+    if (cell_index[k] >= R) throw std::invalid_argument("recover_cells: index out of range");
+    if (seen[cell_index[k]]) throw std::invalid_argument("recover_cells: a cell given twice");
+    seen[cell_index[k]] = true;
+    for (size_t j = 0; j < l; j++) std::memcpy(&y[4 * (k * l + j)], values[k][j].v.data(), 32);
+  }
+  const std::vector<uint32_t> blob(m, 0);
+  const int flags = KZGX_PROVE_COSETS_EXTENDED | (bit_reversed ? KZGX_NTT_BITREV : 0);
+  int ok = 0;
+  if (proofs) {
+    const int nl = base_limbs();
+    std::vector<uint64_t> pxy(2 * nl * R);
+    std::vector<int> inf(R);
+    check(kzgx_recover_cells_and_proofs(ctx, blob.data(), cell_index.data(), y.data(), m, 1, log2n, kl, flags,
+                                        out.data(), nullptr, pxy.data(), inf.data(), &ok),
+          "kzgx_recover_cells_and_proofs");
+    proofs->clear();
+    for (size_t j = 0; j < R; j++) proofs->push_back(proof(to_g1(&pxy[2 * nl * j], inf[j])));
+  } else {
+    check(kzgx_recover_cells(ctx, blob.data(), cell_index.data(), y.data(), m, 1, log2n, kl, flags, out.data(),
+                             nullptr, &ok),
+          "kzgx_recover_cells");
+  }
+  if (!ok) throw std::domain_error("recover_cells: the cells lie on no polynomial of fewer than 2^log2n coefficients");
+  std::vector<Fr> res(D);
+  for (size_t i = 0; i < D; i++) std::memcpy(res[i].v.data(), &out[4 * i], 32);
+  return res;
+}
+
+std::vector<Fr> trusted_setup::recover_cells(const std::vector<uint32_t>& cell_index,
+                                             const std::vector<std::vector<Fr>>& values, unsigned log2n,
+                                             bool bit_reversed) {
+  return recovered(cell_index, values, log2n, bit_reversed, nullptr);
+}
+
+std::pair<std::vector<Fr>, std::vector<proof>> trusted_setup::recover_cells_and_proofs(
+    const std::vector<uint32_t>& cell_index, const std::vector<std::vector<Fr>>& values, unsigned log2n,
+    bool bit_reversed) {
+  std::vector<proof> proofs;
+  std::vector<Fr> y = recovered(cell_index, values, log2n, bit_reversed, &proofs);
+  return {std::move(y), std::move(proofs)};
+}
+
 G1 trusted_setup::linear_combination(const std::vector<G1>& points, const std::vector<Fr>& scalars) {
   const size_t m = points.size();
   if (scalars.size() != m) throw std::invalid_argument("linear_combination: size mismatch");

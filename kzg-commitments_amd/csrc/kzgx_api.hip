@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "curve_consts.h"
+#include "fr_host.hpp"
 #include "kzgx_internal.hpp"
 #include "kzgx_setup.hpp"
 
@@ -612,7 +613,7 @@ void kzgx_destroy(kzgx_ctx* ctx) {
     void* wb[] = {w.counts, w.offsets, w.cursors, w.entries, w.bsum,  w.heads,
                   w.tails,  w.tailk,   w.rt,      w.q,       w.parts, w.fpart, w.fsum, w.gpart, w.gmeta, w.sstate, w.qbig,
                   w.lat_cnt, w.var_tab, w.var_parts, w.var_scal, w.var_pt, w.var_inf, w.ntt_tmp, w.ntt_coef,
-                  w.g1n_rec, w.fk_c, w.fkm_y, w.jidx};
+                  w.g1n_rec, w.fk_c, w.fkm_y, w.jidx, w.rec_w, w.rec_coef, w.rec_aux};
     for (void* p : wb)
       if (p) (void)hipFree(p);
     if (w.done) (void)hipEventDestroy(w.done);
@@ -2208,44 +2209,7 @@ int kzgx_prove_all_batch(kzgx_ctx* ctx, const uint64_t* in, unsigned log2n, size
 }  // extern "C"
 
 namespace {
-// host Montgomery product over Fr, 8 x 32-bit limbs: out = a b 2^-256 mod r (out may alias a or b)
-template <class FR>
-void fr_host_mmul(const uint32_t* a, const uint32_t* b, uint32_t* out) {
-  uint32_t t[10] = {0};
-  for (int i = 0; i < 8; i++) {
-    uint64_t c = 0, s;
-    for (int j = 0; j < 8; j++) {
-      s = (uint64_t)a[j] * b[i] + t[j] + c;
-      t[j] = (uint32_t)s;
-      c = s >> 32;
-    }
-    s = (uint64_t)t[8] + c;
-    t[8] = (uint32_t)s;
-    t[9] = (uint32_t)(s >> 32);
-    const uint32_t q = t[0] * FR::INV;
-    c = ((uint64_t)q * FR::P[0] + t[0]) >> 32;
-    for (int j = 1; j < 8; j++) {
-      s = (uint64_t)q * FR::P[j] + t[j] + c;
-      t[j - 1] = (uint32_t)s;
-      c = s >> 32;
-    }
-    s = (uint64_t)t[8] + c;
-    t[7] = (uint32_t)s;
-    t[8] = t[9] + (uint32_t)(s >> 32);
-  }
-  bool ge = t[8] != 0;  // t < 2 r
-  if (!ge) {
-    int i = 7;
-    while (i >= 0 && t[i] == FR::P[i]) i--;
-    ge = i < 0 || t[i] > FR::P[i];
-  }
-  uint64_t borrow = 0;
-  for (int i = 0; i < 8; i++) {
-    const uint64_t d = (uint64_t)t[i] - (ge ? FR::P[i] : 0u) - borrow;
-    out[i] = (uint32_t)d;
-    borrow = (d >> 32) & 1;
-  }
-}
+using kzgx::fr_host_mmul;  // fr_host.hpp
 
 // xs[q] = the point of offset q in chunk `index` of y: w_D^(i + R j), with bitrev i = brev_R(index), j = brev_l(q)
 template <class FR, class T>
@@ -2584,6 +2548,143 @@ int kzgx_verify_cells_aggregate_checked(kzgx_ctx* ctx, const uint64_t* commits_x
                                         int flags, int subgroup, int* ok) {
   return verify_cells_host(ctx, commits_xy, commit_inf, n_commits, commit_index, cell_index, proofs_xy, proof_inf, ys,
                            challenges, count, log2n, log2l, flags, true, subgroup, ok);
+}
+
+}  // extern "C"
+
+// ---- cell recovery ----------------------------------------------------------------------------
+namespace {
+// the argument checks shared by the four entries (proofs: also the SRS the openings need)
+int recover_args(kzgx_ctx* ctx, size_t count, size_t n_blobs, unsigned log2n, unsigned log2l, int flags, bool proofs) {
+  const int mx = kzgx::ntt_max_log2(ctx->c.curve);
+  if (flags & ~(KZGX_NTT_BITREV | KZGX_PROVE_COSETS_EXTENDED)) return KZGX_ERR_ARG;
+  if (!(flags & KZGX_PROVE_COSETS_EXTENDED)) return KZGX_ERR_ARG;  // no redundancy to recover from
+  if (mx < 0 || log2n > 31 || log2l > log2n || (int)log2n + 1 > mx) return KZGX_ERR_ARG;
+  if (log2n + 1 - log2l > KZGX_RECOVER_MAX_LOG2_CELLS) return KZGX_ERR_ARG;
+  if (count > 0xfffffffeu || n_blobs > 0xffffffffu || count > (SIZE_MAX >> 6 >> log2l) ||
+      n_blobs > (SIZE_MAX >> 9 >> log2n))
+    return KZGX_ERR_ARG;
+  if (proofs) {
+    size_t n = 0;
+    KZGX_TRY(prove_cosets_args(ctx, log2n, log2l, (size_t)-1, flags, &n));
+  }
+  return KZGX_OK;
+}
+
+int recover_device(kzgx_ctx* ctx, const void* d_blob_index, const void* d_cell_index, const void* d_ys, size_t count,
+                   size_t n_blobs, unsigned log2n, unsigned log2l, int flags, void* d_out_y, void* d_out_coeffs,
+                   bool proofs, void* d_out_proofs_xy, void* d_out_proofs_is_inf, void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (n_blobs == 0) return KZGX_OK;
+  KZGX_TRY(recover_args(ctx, count, n_blobs, log2n, log2l, flags, proofs));
+  if (!d_ok || (count > 0 && (!d_blob_index || !d_cell_index || !d_ys))) return KZGX_ERR_ARG;
+  if (proofs ? (!d_out_proofs_xy || !d_out_proofs_is_inf) : (!d_out_y && !d_out_coeffs)) return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const size_t n = (size_t)1 << log2n, D = 2 * n, R = D >> log2l, pw = point_words(ctx);
+  const bool bitrev = (flags & KZGX_NTT_BITREV) != 0;
+  // chunks of blobs, so that every workspace of the call is bounded
+  const size_t chunk = std::max<size_t>(1, kzgx::RECOVER_CHUNK_SCALARS >> (log2n + 1));
+  for (size_t b0 = 0; b0 < n_blobs; b0 += chunk) {
+    const size_t cb = std::min(chunk, n_blobs - b0);
+    uint32_t* oc = d_out_coeffs ? (uint32_t*)d_out_coeffs + b0 * n * 8 : nullptr;
+    KZGX_TRY(kzgx::recover_cells(&ctx->c, *ws, (const uint32_t*)d_blob_index, (const uint32_t*)d_cell_index,
+                                 (const uint32_t*)d_ys, count, n_blobs, b0, cb, log2n, log2l, bitrev, proofs,
+                                 d_out_y ? (uint32_t*)d_out_y + b0 * D * 8 : nullptr, oc, (uint32_t*)d_ok + b0, st));
+    if (proofs)  // the coefficients stay on the device; a failed blob's are zero, its proofs infinity
+      KZGX_TRY(kzgx_prove_cosets_batch_device(ctx, oc ? oc : ws->rec_coef, log2n, log2l, cb, n, flags,
+                                              (uint32_t*)d_out_proofs_xy + b0 * R * pw,
+                                              (uint32_t*)d_out_proofs_is_inf + b0 * R, nullptr, st));
+  }
+  return KZGX_OK;
+}
+
+int recover_host(kzgx_ctx* ctx, const uint32_t* blob_index, const uint32_t* cell_index, const uint64_t* ys,
+                 size_t count, size_t n_blobs, unsigned log2n, unsigned log2l, int flags, uint64_t* out_y,
+                 uint64_t* out_coeffs, bool proofs, uint64_t* out_proofs_xy, int* out_proofs_is_inf, int* ok) {
+  KZGX_TRY(activate(ctx));
+  if (n_blobs == 0) return KZGX_OK;
+  KZGX_TRY(recover_args(ctx, count, n_blobs, log2n, log2l, flags, proofs));
+  if (!ok || (count > 0 && (!blob_index || !cell_index || !ys))) return KZGX_ERR_ARG;
+  if (proofs ? (!out_proofs_xy || !out_proofs_is_inf) : (!out_y && !out_coeffs)) return KZGX_ERR_ARG;
+  const size_t n = (size_t)1 << log2n, D = 2 * n, R = D >> log2l;
+  {  // every index in range, no (blob, cell) twice, at least R / 2 cells per blob
+    std::vector<uint8_t> seen(n_blobs * R, 0);
+    std::vector<uint32_t> cnt(n_blobs, 0);
+    for (size_t k = 0; k < count; k++) {
+      if (blob_index[k] >= n_blobs || cell_index[k] >= R) return KZGX_ERR_ARG;
+      uint8_t& s = seen[(size_t)blob_index[k] * R + cell_index[k]];
+      if (s) return KZGX_ERR_ARG;
+      s = 1;
+      cnt[blob_index[k]]++;
+    }
+    for (size_t b = 0; b < n_blobs; b++)
+      if (cnt[b] < R / 2) return KZGX_ERR_ARG;
+  }
+  const size_t yb = (count << log2l) * 32, ib = align256(count * 4), oyb = out_y ? n_blobs * D * 32 : 0,
+               ocb = out_coeffs ? n_blobs * n * 32 : 0, pb = proofs ? n_blobs * R * point_words(ctx) * 4 : 0,
+               pfb = proofs ? n_blobs * R * 4 : 0;
+  void *d_s, *d_i, *d_o, *d_p;
+  KZGX_TRY(stage(ctx, 0, yb + 16, &d_s));
+  KZGX_TRY(stage(ctx, 1, 2 * ib + n_blobs * 4, &d_i));  // blob_index | cell_index | ok
+  KZGX_TRY(stage(ctx, 2, oyb + ocb + 16, &d_o));        // out_y | out_coeffs
+  KZGX_TRY(stage(ctx, 3, align256(pb) + pfb + 16, &d_p));
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_s, ys, yb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_i, blob_index, count * 4, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync((char*)d_i + ib, cell_index, count * 4, hipMemcpyHostToDevice, st));
+  void* d_ok = (char*)d_i + 2 * ib;
+  void* d_oy = out_y ? d_o : nullptr;
+  void* d_oc = out_coeffs ? (char*)d_o + oyb : nullptr;
+  KZGX_TRY(recover_device(ctx, d_i, (char*)d_i + ib, d_s, count, n_blobs, log2n, log2l, flags, d_oy, d_oc, proofs, d_p,
+                          (char*)d_p + align256(pb), d_ok, st));
+  std::vector<uint32_t> okw(n_blobs), inf(proofs ? n_blobs * R : 0);
+  if (out_y) KZGX_TRY_HIP(hipMemcpyAsync(out_y, d_oy, oyb, hipMemcpyDeviceToHost, st));
+  if (out_coeffs) KZGX_TRY_HIP(hipMemcpyAsync(out_coeffs, d_oc, ocb, hipMemcpyDeviceToHost, st));
+  if (proofs) {
+    KZGX_TRY_HIP(hipMemcpyAsync(out_proofs_xy, d_p, pb, hipMemcpyDeviceToHost, st));
+    KZGX_TRY_HIP(hipMemcpyAsync(inf.data(), (char*)d_p + align256(pb), pfb, hipMemcpyDeviceToHost, st));
+  }
+  KZGX_TRY_HIP(hipMemcpyAsync(okw.data(), d_ok, n_blobs * 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t b = 0; b < n_blobs; b++) ok[b] = okw[b] ? 1 : 0;
+  for (size_t i = 0; i < inf.size(); i++) out_proofs_is_inf[i] = (int)inf[i];
+  return KZGX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kzgx_recover_cells_device(kzgx_ctx* ctx, const void* d_blob_index, const void* d_cell_index, const void* d_ys,
+                              size_t count, size_t n_blobs, unsigned log2n, unsigned log2l, int flags,
+                              void* d_out_y, void* d_out_coeffs, void* d_ok, void* stream) {
+  return recover_device(ctx, d_blob_index, d_cell_index, d_ys, count, n_blobs, log2n, log2l, flags, d_out_y,
+                        d_out_coeffs, false, nullptr, nullptr, d_ok, stream);
+}
+
+int kzgx_recover_cells_and_proofs_device(kzgx_ctx* ctx, const void* d_blob_index, const void* d_cell_index,
+                                         const void* d_ys, size_t count, size_t n_blobs, unsigned log2n,
+                                         unsigned log2l, int flags, void* d_out_y, void* d_out_coeffs,
+                                         void* d_out_proofs_xy, void* d_out_proofs_is_inf, void* d_ok,
+                                         void* stream) {
+  return recover_device(ctx, d_blob_index, d_cell_index, d_ys, count, n_blobs, log2n, log2l, flags, d_out_y,
+                        d_out_coeffs, true, d_out_proofs_xy, d_out_proofs_is_inf, d_ok, stream);
+}
+
+int kzgx_recover_cells(kzgx_ctx* ctx, const uint32_t* blob_index, const uint32_t* cell_index, const uint64_t* ys,
+                       size_t count, size_t n_blobs, unsigned log2n, unsigned log2l, int flags, uint64_t* out_y,
+                       uint64_t* out_coeffs, int* ok) {
+  return recover_host(ctx, blob_index, cell_index, ys, count, n_blobs, log2n, log2l, flags, out_y, out_coeffs, false,
+                      nullptr, nullptr, ok);
+}
+
+int kzgx_recover_cells_and_proofs(kzgx_ctx* ctx, const uint32_t* blob_index, const uint32_t* cell_index,
+                                  const uint64_t* ys, size_t count, size_t n_blobs, unsigned log2n, unsigned log2l,
+                                  int flags, uint64_t* out_y, uint64_t* out_coeffs, uint64_t* out_proofs_xy,
+                                  int* out_proofs_is_inf, int* ok) {
+  return recover_host(ctx, blob_index, cell_index, ys, count, n_blobs, log2n, log2l, flags, out_y, out_coeffs, true,
+                      out_proofs_xy, out_proofs_is_inf, ok);
 }
 
 }  // extern "C"

@@ -69,6 +69,10 @@ struct MsmWs {
   // coset openings (g1_ntt.hip): a chunk's zero-padded coefficients / natural-order values for y
   uint32_t* fkm_y = nullptr;
   size_t fkm_y_b = 0;
+  // cell recovery (recover.hip): a chunk's size-D arrays (transformed in place), its
+  // coefficients when the caller takes none, and the locator values / cell map / flags
+  uint32_t *rec_w = nullptr, *rec_coef = nullptr, *rec_aux = nullptr;
+  size_t rec_w_b = 0, rec_coef_b = 0, rec_aux_b = 0;
   size_t counts_b = 0, offsets_b = 0, cursors_b = 0, entries_b = 0, bsum_b = 0, heads_b = 0, tails_b = 0, tailk_b = 0,
          rt_b = 0, q_b = 0, parts_b = 0, fpart_b = 0, fsum_b = 0, gpart_b = 0, gmeta_b = 0, sstate_b = 0, qbig_b = 0;
   hipStream_t owner = nullptr;  // workspaces are per stream so calls on
@@ -450,6 +454,17 @@ int prove_cosets_setup(Ctx* ctx, MsmWs& ws, const uint32_t* d_srs_canon, unsigne
 int prove_cosets(Ctx* ctx, MsmWs& ws, const uint32_t* d_srs_canon, const uint32_t* d_coeffs, size_t stride,
                  unsigned log2n, unsigned log2l, size_t batch, bool ext, bool bitrev, uint32_t* d_out_xy,
                  uint32_t* d_out_inf, uint32_t* d_y, hipStream_t st);
+
+// cell recovery (recover.hip): blobs b0 .. b0 + cb - 1 of a call (cb 2^(log2n + 1) <=
+// max(RECOVER_CHUNK_SCALARS, 2^(log2n + 1))) from the flat cell list of the whole call;
+// d_out_y / d_out_coeffs / d_ok point at blob b0's entries.  d_out_y and d_out_coeffs
+// may be null; with want_coef and no d_out_coeffs the coefficients (zero for a failed
+// blob) are left in ws.rec_coef, packed, for the proofs.  ws: the caller's lease on st.
+constexpr size_t RECOVER_CHUNK_SCALARS = KZGX_RECOVER_CHUNK_SCALARS;
+int recover_cells(Ctx* ctx, MsmWs& ws, const uint32_t* d_blob_index, const uint32_t* d_cell_index,
+                  const uint32_t* d_ys, size_t count, size_t n_blobs, size_t b0, size_t cb, unsigned log2n,
+                  unsigned log2l, bool bitrev, bool want_coef, uint32_t* d_out_y, uint32_t* d_out_coeffs,
+                  uint32_t* d_ok, hipStream_t st);
 
 // verify path: G2 SRS, polyeval_G2, pairing (pairing.hip)
 int gen_srs_g2_points(Ctx* ctx, const uint32_t* d_tau, size_t start, size_t n, uint32_t* d_out, hipStream_t st);

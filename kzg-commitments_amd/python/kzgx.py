@@ -44,6 +44,8 @@ EXPORTS = [
     "kzgx_coset_points", "kzgx_prove_cosets_prepare", "kzgx_prove_cosets_batch", "kzgx_prove_cosets_batch_device",
     "kzgx_verify_cells_aggregate", "kzgx_verify_cells_aggregate_device", "kzgx_verify_cells_aggregate_checked",
     "kzgx_verify_cells_aggregate_checked_device",
+    "kzgx_recover_cells", "kzgx_recover_cells_device", "kzgx_recover_cells_and_proofs",
+    "kzgx_recover_cells_and_proofs_device",
 ]
 
 
@@ -66,6 +68,9 @@ PROVE_ALL_EVALS = _header_define("KZGX_PROVE_ALL_EVALS")
 G1_NTT_CHUNK_POINTS = _header_define("KZGX_G1_NTT_CHUNK_POINTS")
 # coset openings: the cosets are those of the size-2n domain
 PROVE_COSETS_EXTENDED = _header_define("KZGX_PROVE_COSETS_EXTENDED")
+# cell recovery: the most cells per blob (log2), and the scalars per internal chunk of blobs
+RECOVER_MAX_LOG2_CELLS = _header_define("KZGX_RECOVER_MAX_LOG2_CELLS")
+RECOVER_CHUNK_SCALARS = _header_define("KZGX_RECOVER_CHUNK_SCALARS")
 
 _lib = None
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -210,6 +215,16 @@ def lib():
             "kzgx_verify_cells_aggregate_checked_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz,
                                                                           ctypes.c_uint, ctypes.c_uint, ctypes.c_int,
                                                                           ctypes.c_int, vp, vp]),
+            "kzgx_recover_cells": (ctypes.c_int, [vp, u32p, u32p, u64p, sz, sz, ctypes.c_uint, ctypes.c_uint,
+                                                  ctypes.c_int, u64p, u64p, intp]),
+            "kzgx_recover_cells_device": (ctypes.c_int, [vp, vp, vp, vp, sz, sz, ctypes.c_uint, ctypes.c_uint,
+                                                         ctypes.c_int, vp, vp, vp, vp]),
+            "kzgx_recover_cells_and_proofs": (ctypes.c_int, [vp, u32p, u32p, u64p, sz, sz, ctypes.c_uint,
+                                                             ctypes.c_uint, ctypes.c_int, u64p, u64p, u64p, intp,
+                                                             intp]),
+            "kzgx_recover_cells_and_proofs_device": (ctypes.c_int, [vp, vp, vp, vp, sz, sz, ctypes.c_uint,
+                                                                    ctypes.c_uint, ctypes.c_int, vp, vp, vp, vp, vp,
+                                                                    vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -995,3 +1010,65 @@ class Context:
             self.h, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index, d_proofs, d_proof_inf, d_ys,
             d_challenges, count, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), int(bool(subgroup)), d_ok,
             stream), "kzgx_verify_cells_aggregate_checked_device")
+
+    # ---- cell recovery ----
+    def _recover_host(self, proofs, blob_index, cell_index, ys, n_blobs, log2n, extended, bitrev, want_y,
+                      want_coeffs):
+        y = np.ascontiguousarray(ys, dtype=np.uint64)
+        assert y.ndim >= 2 and y.shape[-1] == 4
+        l = y.shape[-2]
+        log2l = _log2_exact(l)
+        y = y.reshape(-1, l, 4)
+        cnt = y.shape[0]
+        bi = np.ascontiguousarray(blob_index, dtype=np.uint32).reshape(-1)
+        ki = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)
+        assert bi.shape[0] == cnt and ki.shape[0] == cnt
+        n = 1 << log2n
+        R = max(1, (2 * n) >> log2l)
+        oy = np.zeros((n_blobs, R, l, 4), dtype=np.uint64) if want_y else None
+        oc = np.zeros((n_blobs, n, 4), dtype=np.uint64) if want_coeffs else None
+        ok = np.zeros(n_blobs, dtype=np.int32)
+        head = (self.h, bi.ctypes.data_as(u32p) if cnt else None, ki.ctypes.data_as(u32p) if cnt else None,
+                _p(y) if cnt else None, cnt, n_blobs, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), _p(oy),
+                _p(oc))
+        if not proofs:
+            _chk(lib().kzgx_recover_cells(*head, ok.ctypes.data_as(intp)), "kzgx_recover_cells")
+            return oy, oc, ok.astype(bool)
+        xy = np.zeros((n_blobs, R, 2 * self.w64), dtype=np.uint64)
+        inf = np.zeros((n_blobs, R), dtype=np.int32)
+        _chk(lib().kzgx_recover_cells_and_proofs(*head, _p(xy), inf.ctypes.data_as(intp), ok.ctypes.data_as(intp)),
+             "kzgx_recover_cells_and_proofs")
+        return oy, oc, xy, inf.astype(bool), ok.astype(bool)
+
+    def recover_cells(self, blob_index, cell_index, ys, n_blobs, log2n, extended=True, bitrev=False, want_y=True,
+                      want_coeffs=True):
+        """kzgx_recover_cells: rebuild n_blobs polynomials of 2^log2n coefficients from at least half of the
+        R = 2^(log2n + 1) / l cells of each.  blob_index / cell_index (count,), ys (count, l, 4) with l taken from
+        the shape, a flat list as verify_cells_aggregate takes it (bitrev: cell_index is the chunk of the
+        bit-reversed evaluation array and ys is in its order) -> (y (n_blobs, R, l, 4) in prove_cosets' layout or
+        None, coeffs (n_blobs, n, 4) or None, ok (n_blobs,) bool).  A blob with ok False is all zero."""
+        return self._recover_host(False, blob_index, cell_index, ys, n_blobs, log2n, extended, bitrev, want_y,
+                                  want_coeffs)
+
+    def recover_cells_and_proofs(self, blob_index, cell_index, ys, n_blobs, log2n, extended=True, bitrev=False,
+                                 want_y=True, want_coeffs=True):
+        """kzgx_recover_cells_and_proofs: recover_cells plus every cell's proof, prove_cosets' (xy, is_inf) of the
+        recovered polynomials -> (y, coeffs, xy (n_blobs, R, 2 w64), is_inf (n_blobs, R), ok)."""
+        return self._recover_host(True, blob_index, cell_index, ys, n_blobs, log2n, extended, bitrev, want_y,
+                                  want_coeffs)
+
+    def recover_cells_device(self, d_blob_index, d_cell_index, d_ys, count, n_blobs, log2n, log2l, d_out_y,
+                             d_out_coeffs, d_ok, extended=True, bitrev=False, stream=None):
+        """kzgx_recover_cells_device: device pointers (uint32 indices, d_ok n_blobs uint32), enqueued on stream."""
+        _chk(lib().kzgx_recover_cells_device(self.h, d_blob_index, d_cell_index, d_ys, count, n_blobs, log2n, log2l,
+                                             _cosets_flags(extended, bitrev=bitrev), d_out_y, d_out_coeffs, d_ok,
+                                             stream), "kzgx_recover_cells_device")
+
+    def recover_cells_and_proofs_device(self, d_blob_index, d_cell_index, d_ys, count, n_blobs, log2n, log2l,
+                                        d_out_y, d_out_coeffs, d_out_xy, d_out_inf, d_ok, extended=True,
+                                        bitrev=False, stream=None):
+        """kzgx_recover_cells_and_proofs_device: the same with the n_blobs x R proofs and their uint32 flags."""
+        _chk(lib().kzgx_recover_cells_and_proofs_device(
+            self.h, d_blob_index, d_cell_index, d_ys, count, n_blobs, log2n, log2l,
+            _cosets_flags(extended, bitrev=bitrev), d_out_y, d_out_coeffs, d_out_xy, d_out_inf, d_ok, stream),
+            "kzgx_recover_cells_and_proofs_device")

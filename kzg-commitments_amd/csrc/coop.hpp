@@ -67,8 +67,10 @@ KZGX_DEV Xyzz<C> coop_dbl(const Xyzz<C>& p, uint32_t* sc, int j) {
   const F29<F> xx = f29_lds_ld<F>(b1 + L);
   const F29<F> M = f29_add<F>(f29_add<F>(xx, xx), xx);  // < 6m
   {
-    const F29<F> A = j == 0 ? U : j == 1 ? p.X : j == 2 ? M : V;
-    const F29<F> B = j <= 1 ? V : j == 2 ? M : p.ZZ;
+    // per-limb selects (f29_sel): a conditional expression over the structs
+    // selects between their addresses and keeps them in scratch memory
+    const F29<F> A = f29_sel<F>(j == 0, U, f29_sel<F>(j == 1, p.X, f29_sel<F>(j == 2, M, V)));
+    const F29<F> B = f29_sel<F>(j <= 1, V, f29_sel<F>(j == 2, M, p.ZZ));
     f29_lds_st<F>(b2 + j * L, f29_mul<F>(A, B));
   }
   coop_fence();
@@ -108,8 +110,12 @@ KZGX_DEV Xyzz<C> coop_add(const Xyzz<C>& p, const Xyzz<C>& q, uint32_t* sc, int 
   uint32_t* b4 = sc + 24 * L;
   uint32_t* bx = sc + 32 * L;
   {
-    const F29<F> A = j == 0 ? p.X : j == 1 ? q.X : j == 2 ? p.Y : j == 3 ? q.Y : j == 4 ? p.ZZ : p.ZZZ;
-    const F29<F> B = j == 0 ? q.ZZ : j == 1 ? p.ZZ : j == 2 ? q.ZZZ : j == 3 ? p.ZZZ : j == 4 ? q.ZZ : q.ZZZ;
+    const F29<F> A = f29_sel<F>(
+        j == 0, p.X,
+        f29_sel<F>(j == 1, q.X, f29_sel<F>(j == 2, p.Y, f29_sel<F>(j == 3, q.Y, f29_sel<F>(j == 4, p.ZZ, p.ZZZ)))));
+    const F29<F> B = f29_sel<F>(
+        j == 0, q.ZZ,
+        f29_sel<F>(j == 1, p.ZZ, f29_sel<F>(j == 2, q.ZZZ, f29_sel<F>(j == 3, p.ZZZ, f29_sel<F>(j == 4, q.ZZ, q.ZZZ)))));
     f29_lds_st<F>(b1 + j * L, f29_mul<F>(A, B));
   }
   coop_fence();

@@ -1,0 +1,120 @@
+// Horner pass of the block-table MSM (msm_joint.hip): the 254 / 255 plane
+// sums A_w of each MSM (and block range) folded into sum_w 2^w A_w.
+//
+// The pass is under 2% of a call's point operations and all of its
+// dependent chain: bits(r) - 1 doublings per MSM that no lane mapping
+// removes.  What the mapping decides is what one link of the chain costs: a
+// lone lane issues a doubling's 9 products one after another (~5 us in a
+// wavefront with nothing else to run), an aligned group of 8 lanes
+// (coop.hpp) runs them in 3 rounds.  So
+//   stage 1  one lane per (MSM, range, segment of JOINT_SEG planes), many
+//            short independent chains: S = sum_t 2^t A_{SEG seg + t};
+//   stage 2  one 8-lane group per MSM walks the segments from the top:
+//            JOINT_SEG cooperative doublings, then one cooperative addition
+//            per range: sum_seg 2^(SEG seg) sum_rho S.
+// The sum over planes is linear, so the ranges fold apart in stage 1 and
+// meet in stage 2.  k_fixed_finish converts the sums (its lone-lane
+// inversion inside stage 2 would run in 8 of a wavefront's 64 lanes and only
+// lengthen the chain).
+//
+// Compiled with memory clauses off, as latency.hip and for its reason: the
+// cooperative operations inlined next to clause-formed loads (DESIGN.md
+// section 7).
+#ifndef KZGX_MEMCLAUSE_OFF
+#error "joint_horner.hip needs -mllvm -amdgpu-max-memory-clause=1 -DKZGX_MEMCLAUSE_OFF (see the Makefile)"
+#endif
+#include <hip/hip_runtime.h>
+
+#include "coop.hpp"
+#include "curve.hpp"
+#include "kzgx_internal.hpp"
+#include "kzgx_setup.hpp"
+
+namespace kzgx {
+
+// stage 1: lane (b, rho, seg) folds the planes [SEG seg, min(SEG seg + SEG,
+// bits)) of range rho of MSM b, highest plane first.  Lanes hold independent
+// segments, so a lane's SEG - 1 doublings and additions are not a
+// wavefront's.  The next plane's partial is loaded ahead of the doubling it
+// follows.  Layouts: part[b][rho][plane], segs[b][rho][seg].
+template <class C>
+__global__ __launch_bounds__(64) void k_joint_horner1(const uint32_t* __restrict__ part, uint64_t lanes,
+                                                      uint32_t* __restrict__ segs) {
+  constexpr int XW = xyzz_words<C>();
+  constexpr uint32_t BITS = C::SCALAR_BITS;
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= lanes) return;  // lanes = batch R JOINT_NSEG
+  const uint64_t br = t / JOINT_NSEG;
+  const uint32_t seg = (uint32_t)(t % JOINT_NSEG);
+  const uint32_t lo = JOINT_SEG * seg, hi = lo + JOINT_SEG < BITS ? lo + JOINT_SEG : BITS;
+  const uint32_t* p = part + br * JOINT_PL * XW;
+  Xyzz<C> acc = xyzz_load<C>(p + (size_t)(hi - 1) * XW);
+  for (uint32_t w = hi - 1; w-- > lo;) {
+    const Xyzz<C> a = xyzz_load<C>(p + (size_t)w * XW);
+    acc = xyzz_dbl<C>(acc);
+    acc = xyzz_add<C>(acc, a);
+  }
+  xyzz_store<C>(segs + t * XW, acc);
+}
+
+// stage 2: the aligned 8-lane group (b) folds its R x JOINT_NSEG segment
+// sums, 8 groups per workgroup.  Every lane of a group loads the same
+// records and runs the same branches, so coop.hpp's contract holds: a group
+// past the batch leaves before it touches LDS, and the infinity, doubling
+// and cancel returns of the cooperative operations depend on the group's
+// point alone.  Fixed trip counts; the first range's sum of the next segment
+// is loaded ahead of the doublings it follows.
+template <class C>
+__global__ __launch_bounds__(64) void k_joint_horner2(const uint32_t* __restrict__ segs, uint32_t batch, uint32_t R,
+                                                      uint32_t* __restrict__ sums) {
+  constexpr int XW = xyzz_words<C>();
+  constexpr int L = C::Fp29::L;
+  __shared__ uint32_t sc[(64 / COOP_G) * COOP_SLOTS * L];
+  const uint32_t grp = threadIdx.x / COOP_G;
+  const int j = (int)(threadIdx.x % COOP_G);
+  const uint32_t b = blockIdx.x * (64 / COOP_G) + grp;
+  if (b >= batch) return;
+  uint32_t* my = sc + grp * COOP_SLOTS * L;
+  const uint32_t* p = segs + (size_t)b * R * JOINT_NSEG * XW;
+  auto seg_sum = [&](uint32_t r, uint32_t seg) __attribute__((always_inline)) {
+    return xyzz_load<C>(p + ((size_t)r * JOINT_NSEG + seg) * XW);
+  };
+  Xyzz<C> acc = seg_sum(0, JOINT_NSEG - 1);
+#pragma unroll 1
+  for (uint32_t r = 1; r < R; r++) acc = coop_add<C>(acc, seg_sum(r, JOINT_NSEG - 1), my, j);
+#pragma unroll 1
+  for (uint32_t seg = JOINT_NSEG - 1; seg-- > 0;) {
+    const Xyzz<C> nxt = seg_sum(0, seg);
+#pragma unroll 1
+    for (uint32_t k = 0; k < JOINT_SEG; k++) acc = coop_dbl<C>(acc, my, j);
+    acc = coop_add<C>(acc, nxt, my, j);
+#pragma unroll 1
+    for (uint32_t r = 1; r < R; r++) acc = coop_add<C>(acc, seg_sum(r, seg), my, j);
+  }
+  if (j == 0) xyzz_store<C>(sums + (size_t)b * XW, acc);
+}
+
+template <class C>
+int joint_horner_launch(const uint32_t* part, uint32_t batch, uint32_t R, uint32_t* segs, uint32_t* sums,
+                        hipStream_t st) {
+  static_assert(C::SCALAR_BITS <= (int)JOINT_PL && C::SCALAR_BITS > (int)(JOINT_PL - JOINT_SEG),
+                "the top segment holds at least one plane");
+  const uint64_t lanes = (uint64_t)batch * R * JOINT_NSEG;
+  if (batch == 0 || R == 0 || (lanes + 63) / 64 > 0x7fffffffull) return KZGX_ERR_ARG;
+  hipLaunchKernelGGL(k_joint_horner1<C>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, part, lanes, segs);
+  constexpr uint32_t GPW = 64 / COOP_G;  // groups per workgroup
+  hipLaunchKernelGGL(k_joint_horner2<C>, dim3((batch + GPW - 1) / GPW), dim3(64), 0, st, segs, batch, R, sums);
+  return KZGX_OK;
+}
+template int joint_horner_launch<BN254G1>(const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t*, hipStream_t);
+template int joint_horner_launch<BLS12381G1>(const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t*, hipStream_t);
+
+// device bring-up (kzgx_setup.hpp): one launch loads this code object
+__global__ void k_warm_joint_horner() {}
+int warm_joint_horner(hipStream_t st) {
+  hipLaunchKernelGGL(k_warm_joint_horner, dim3(1), dim3(64), 0, st);
+  KZGX_TRY_HIP(hipGetLastError());
+  return KZGX_OK;
+}
+
+}  // namespace kzgx

@@ -520,7 +520,7 @@ int kzgx_init_device(int curve, int device) {
       kzgx::warm_srs,        kzgx::warm_pairing,    kzgx::warm_verify_wave, kzgx::warm_latency,
       kzgx::warm_fixed_bn_a, kzgx::warm_fixed_bn_b, kzgx::warm_fixed_bn_c,  kzgx::warm_fixed_bn_d,
       kzgx::warm_fixed_bls_a, kzgx::warm_fixed_bls_b, kzgx::warm_fixed_bls_c, kzgx::warm_fixed_bls_d,
-      kzgx::warm_subgroup,   kzgx::warm_msm_joint};
+      kzgx::warm_subgroup,   kzgx::warm_msm_joint,  kzgx::warm_joint_horner};
   for (auto f : warm) KZGX_TRY(f(st));
   // the generator comb tables (per process, per device and curve)
   kzgx::GenTables g;

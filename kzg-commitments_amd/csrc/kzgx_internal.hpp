@@ -367,6 +367,23 @@ void joint_free(JointTable& jt);
 bool joint_serves(const FixedTable& ft, size_t n, size_t batch, bool xyzz_out);
 int joint_msm(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n, size_t batch, size_t stride_words,
               uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st);
+// planes per MSM in the block table path's index and partial arrays (>=
+// SCALAR_BITS; the planes past SCALAR_BITS are never read), and the planes
+// per segment of its Horner pass (joint_horner.hip): stage 1 folds JOINT_SEG
+// planes in a lone lane, stage 2 the JOINT_NSEG segment sums in an 8-lane
+// group.  Chain per MSM: bits - 1 cooperative doublings whatever the
+// segment, JOINT_SEG - 1 lone-lane doublings and additions before them,
+// JOINT_NSEG R cooperative additions among them.  Measured per 2048-MSM BN254
+// launch, stage 1 + stage 2: 4 planes 0.147 + 0.856 ms, 8 planes 0.216 +
+// 0.729 ms, 16 planes 0.261 + 0.649 ms (profiles/joint_horner_serial_kernel_stats_seg*.csv).
+constexpr uint32_t JOINT_PL = 256;
+constexpr uint32_t JOINT_SEG = 16;
+constexpr uint32_t JOINT_NSEG = JOINT_PL / JOINT_SEG;
+static_assert(JOINT_NSEG * JOINT_SEG == JOINT_PL, "whole segments");
+// part[batch][R][JOINT_PL] XYZZ plane sums -> sums[batch] XYZZ; segs: scratch of batch R JOINT_NSEG records
+template <class C>
+int joint_horner_launch(const uint32_t* part, uint32_t batch, uint32_t R, uint32_t* segs, uint32_t* sums,
+                        hipStream_t st);
 int srs_upload(Ctx* ctx, const uint32_t* d_canon, size_t n);
 // mixed additions / s of the fixed-base accumulation loop on L1-resident operands (msm_fixed.hip)
 int microbench_mixed_add(Ctx* ctx, double* rate);

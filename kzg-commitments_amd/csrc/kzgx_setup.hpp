@@ -24,6 +24,7 @@ int warm_verify_wave(hipStream_t st);
 int warm_latency(hipStream_t st);
 int warm_subgroup(hipStream_t st);
 int warm_msm_joint(hipStream_t st);
+int warm_joint_horner(hipStream_t st);
 // the fixed-base MSM's per-window objects (msm_fixed_inst.hip, one per group)
 int warm_fixed_bn_a(hipStream_t st);
 int warm_fixed_bn_b(hipStream_t st);

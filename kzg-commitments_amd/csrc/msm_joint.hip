@@ -29,7 +29,7 @@
 // Passes of one call (profiler scopes):
 //   k_joint_index   (msm_scatter)  one 32-bit word per (block, plane)
 //   k_joint_accum   (msm_accum)    lane (MSM, plane) sums its plane's entries
-//   k_joint_horner1/2 + k_fixed_finish (msm_reduce)
+//   k_joint_horner1/2 (joint_horner.hip) + k_fixed_finish (msm_reduce)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,9 +42,6 @@
 
 namespace kzgx {
 
-// planes per MSM in the index and partial arrays (>= SCALAR_BITS; the planes
-// past SCALAR_BITS are never read)
-constexpr uint32_t JOINT_PL = 256;
 constexpr uint32_t JOINT_NEG = 1u << 31;  // index word: negate the entry
 
 // low / high split of a block's m = g_b - 1 non-top points for the build:
@@ -453,47 +450,7 @@ __global__ __launch_bounds__(64, fixed_accum_waves<C>()) void k_joint_accum(
   xyzz_store<C>(part + (((size_t)b * R + rho) * JOINT_PL + w) * XW, acc);
 }
 
-// Horner pass, stage 1: lane (b, rho, seg) folds the planes [32 seg, 32 seg +
-// 32) of range rho of MSM b, highest plane first: S = sum_t 2^t A_{32 seg + t}
-// (the sum over planes is linear, so the ranges fold apart and meet in stage
-// 2).  Lanes hold independent segments, so the 31 doublings and additions of
-// a lane are not a wavefront's.  The next plane's partial is loaded ahead of
-// the doubling it follows.
-template <class C>
-__global__ __launch_bounds__(64) void k_joint_horner1(const uint32_t* __restrict__ part, uint32_t count,
-                                                      uint32_t* __restrict__ segs) {
-  constexpr int XW = xyzz_words<C>();
-  constexpr uint32_t BITS = C::SCALAR_BITS;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= count * 8) return;  // count = batch R
-  const uint32_t br = t >> 3, seg = t & 7u;
-  const uint32_t lo = 32 * seg, hi = lo + 32 < BITS ? lo + 32 : BITS;
-  const uint32_t* p = part + (size_t)br * JOINT_PL * XW;
-  Xyzz<C> acc = xyzz_load<C>(p + (size_t)(hi - 1) * XW);
-  for (uint32_t w = hi - 1; w-- > lo;) {
-    const Xyzz<C> a = xyzz_load<C>(p + (size_t)w * XW);
-    acc = xyzz_dbl<C>(acc);
-    acc = xyzz_add<C>(acc, a);
-  }
-  xyzz_store<C>(segs + (size_t)t * XW, acc);
-}
-
-// stage 2: lane b folds its R x 8 segment sums, sum_seg 2^(32 seg) sum_rho S
-template <class C>
-__global__ __launch_bounds__(64) void k_joint_horner2(const uint32_t* __restrict__ segs, uint32_t batch, uint32_t R,
-                                                      uint32_t* __restrict__ sums) {
-  constexpr int XW = xyzz_words<C>();
-  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= batch) return;
-  const uint32_t* p = segs + (size_t)b * R * 8 * XW;
-  Xyzz<C> acc = xyzz_inf<C>();
-  for (int seg = 7; seg >= 0; seg--) {
-    if (seg < 7)
-      for (int k = 0; k < 32; k++) acc = xyzz_dbl<C>(acc);
-    for (uint32_t r = 0; r < R; r++) acc = xyzz_add<C>(acc, xyzz_load<C>(p + ((size_t)r * 8 + seg) * XW));
-  }
-  xyzz_store<C>(sums + (size_t)b * XW, acc);
-}
+// The Horner pass over the partials (part[b][rho][plane]) is joint_horner.hip's.
 
 bool joint_serves(const FixedTable& ft, size_t n, size_t batch, bool xyzz_out) {
   const JointTable& jt = ft.joint;
@@ -506,7 +463,7 @@ static int joint_msm_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, s
                           size_t stride_words, uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st) {
   const JointTable& jt = ft.joint;
   constexpr size_t XB = xyzz_words<C>() * sizeof(uint32_t);
-  static_assert(C::SCALAR_BITS <= (int)JOINT_PL && C::SCALAR_BITS > 224, "4 wavefronts and 8 segments of planes");
+  static_assert(C::SCALAR_BITS <= (int)JOINT_PL && C::SCALAR_BITS > 192, "4 wavefronts of planes");
   const uint32_t nb = (uint32_t)((n + jt.g - 1) / jt.g);  // whole blocks beyond n sum to r (...) = O: skipped
   // block ranges per MSM: 1 unless set (2 halves the last residency's tail
   // but doubles the partials; 2048 MSMs of 4097 points measured 272.1k with 2
@@ -521,7 +478,8 @@ static int joint_msm_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, s
   MsmWs& ws = *wsp;
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.jidx, batch * (size_t)nb * JOINT_PL * 4, &ws.jidx_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.fpart, batch * (size_t)R * JOINT_PL * XB, &ws.fpart_b));
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.fsum, batch * ((size_t)R * 8 + 1) * XB, &ws.fsum_b));
+  // the Horner pass's segment sums [batch][R][JOINT_NSEG], then its [batch] results
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.fsum, batch * ((size_t)R * JOINT_NSEG + 1) * XB, &ws.fsum_b));
   {
     ProfScope p(ctx, st, "msm_scatter");
     hipLaunchKernelGGL(k_joint_index<C>, dim3((nb + 1) / 2, (unsigned)batch), dim3(64), 0, st, d_scalars, (uint32_t)n,
@@ -539,11 +497,8 @@ static int joint_msm_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, s
   }
   {
     ProfScope p(ctx, st, "msm_reduce");
-    uint32_t* sums = ws.fsum + batch * (size_t)R * 8 * xyzz_words<C>();
-    hipLaunchKernelGGL(k_joint_horner1<C>, dim3((unsigned)((batch * R * 8 + 63) / 64)), dim3(64), 0, st, ws.fpart,
-                       (uint32_t)(batch * R), ws.fsum);
-    hipLaunchKernelGGL(k_joint_horner2<C>, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st, ws.fsum,
-                       (uint32_t)batch, R, sums);
+    uint32_t* sums = ws.fsum + batch * (size_t)R * JOINT_NSEG * xyzz_words<C>();
+    KZGX_TRY(joint_horner_launch<C>(ws.fpart, (uint32_t)batch, R, ws.fsum, sums, st));
     fixed_finish_launch<C>(sums, (uint32_t)batch, d_out, d_out_inf, nullptr, st);
   }
   KZGX_TRY_HIP(hipGetLastError());

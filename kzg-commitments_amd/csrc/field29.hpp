@@ -1068,7 +1068,10 @@ __device__ __noinline__ F29<F> f29_inv_vt(const F29<F>& in_, const uint32_t (&)[
       v.v[j] = __builtin_amdgcn_readlane(r.v[j], 3);
     }
   };
-  // 3x the most passes seen: a bound every lane reaches even on a bad input
+  // 3 (2L + 2) passes, 60 / 90: a bound every lane reaches even on a bad
+  // input.  Structured operands (short values, x 2^k, m - 2^k; oracle/field_model.py
+  // inv_vt_trace) need 18 passes on BN254 and 27 on BLS12-381, more than the
+  // random-input figures above.
   for (int pass = 0; pass < 3 * (2 * 29 * L / K + 2) && !f29_is_zero_exact<F>(a); pass++) {
     // n = max(len(a), len(b), 60); the approximations keep bits [0, 29) and
     // [n - 31, n)

@@ -2792,6 +2792,17 @@ extern "C" int kzgx_debug_coop_test(kzgx_ctx* ctx, unsigned* bad) {
   return rc;
 }
 
+namespace kzgx {
+int prim_selftest(int curve, int op, int mode, const uint32_t* in, size_t count, uint32_t* out, hipStream_t st);  // selftest.hip
+}
+// debug: one field / point primitive (selftest.hip PrimOp) on `count` tuples of
+// raw limbs at `in`, the raw limbs of every result to `out`; `mode` picks the
+// active lanes of the wave-uniform forms (0 = all, 1 = lanes 0-3, 2 = lane 0)
+extern "C" int kzgx_debug_prim(kzgx_ctx* ctx, int op, int mode, const uint32_t* in, size_t count, uint32_t* out) {
+  KZGX_TRY(activate(ctx));
+  return kzgx::prim_selftest(ctx->c.curve, op, mode, in, count, out, ctx->c.stream);
+}
+
 extern "C" int kzgx_debug_vw_bench(kzgx_ctx* ctx, int op, unsigned iters, double* res) {
   KZGX_TRY(activate(ctx));
   if (!res || iters == 0) return KZGX_ERR_ARG;

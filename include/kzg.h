@@ -147,6 +147,22 @@ class commit {
    *  entry k was a well-formed point that passed the chosen checks. */
   static std::vector<commit> deserialize_batch(const std::vector<std::vector<uint8_t>>& bytes,
                                                bool check_subgroup = false, std::vector<bool>* valid = nullptr);
+  /** Extension: the bare compressed record of kzg_gpu.h "compressed points"
+   *  (KZGX_ENC_ZCASH: 48 bytes, BLS12-381 only; KZGX_ENC_SEC1: 1 + MODBYTES
+   *  bytes, the compressed counterpart of serialize()'s 0x04 octet).  No u32
+   *  length prefix: the formats are fixed-size.
+   *  @throws std::invalid_argument for an encoding the curve does not offer */
+  std::vector<uint8_t> serialize_compressed(int encoding);
+  /** Extension: `packed` holds whole records of `encoding` back to back; one GPU
+   *  pass decompresses (a square root per record) and checks them all
+   *  (kzgx_g1_decompress_batch).  A record that is malformed, non-canonical,
+   *  without a root or, with check_subgroup, outside the prime-order subgroup
+   *  decodes to infinity with valid[k] = false; the identity record is valid.
+   *  @throws std::invalid_argument for an encoding the curve does not offer or
+   *          a size that is not a multiple of the record length */
+  static std::vector<commit> deserialize_compressed_batch(const std::vector<uint8_t>& packed, int encoding,
+                                                          bool check_subgroup = false,
+                                                          std::vector<bool>* valid = nullptr);
 };
 
 class proof {
@@ -161,6 +177,11 @@ class proof {
   /** Extension: as commit::deserialize_batch. */
   static std::vector<proof> deserialize_batch(const std::vector<std::vector<uint8_t>>& bytes,
                                               bool check_subgroup = false, std::vector<bool>* valid = nullptr);
+  /** Extensions: as commit::serialize_compressed / deserialize_compressed_batch. */
+  std::vector<uint8_t> serialize_compressed(int encoding);
+  static std::vector<proof> deserialize_compressed_batch(const std::vector<uint8_t>& packed, int encoding,
+                                                         bool check_subgroup = false,
+                                                         std::vector<bool>* valid = nullptr);
 };
 
 class trusted_setup {
@@ -168,6 +189,7 @@ class trusted_setup {
   kzgx_ctx* ctx = nullptr;  // device SRS + stream + workspaces
   size_t n = 0;
 
+  trusted_setup() = default;  // from_compressed fills it in
   G1 polyeval_G1(const std::vector<Fr>& P);
   bool aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
                   const std::vector<std::pair<Fr, Fr>>& points, bool checked, bool check_subgroup);
@@ -188,6 +210,18 @@ class trusted_setup {
    *  @throws std::runtime_error for an inaccessible file or a bad G1 record,
    *          std::logic_error for a bad G2 record (as the reference does) */
   trusted_setup(const std::string& filename);
+  /** Extension: a setup from packed compressed points, as published setups
+   *  come: g1 holds 48-byte and g2 96-byte KZGX_ENC_ZCASH records (BLS12-381).
+   *  The counts are independent (a cell verifier's setup has 64 G1 and 65 G2
+   *  points).  Decompressed and checked on the GPU (on the curve, and with
+   *  check_subgroup in the prime-order subgroup), then installed as a loaded
+   *  file's points are; size() is the G1 count.
+   *  @throws std::invalid_argument on BN254, for an empty array or a size that
+   *          is not a multiple of the record length; std::runtime_error for a
+   *          bad or infinite G1 record, std::logic_error for a G2 one (as the
+   *          file constructor does) */
+  static trusted_setup from_compressed(const std::vector<uint8_t>& g1, const std::vector<uint8_t>& g2,
+                                       bool check_subgroup = true);
   ~trusted_setup();
   trusted_setup(const trusted_setup&) = delete;
   trusted_setup& operator=(const trusted_setup&) = delete;
@@ -302,6 +336,17 @@ class trusted_setup {
                            const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
                            const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
                            bool bit_reversed, bool check_subgroup);
+  /** Extension: the checked form on compressed commitments and proofs as they
+   *  travel (kzgx_verify_cells_aggregate_bytes): `commits` and `proofs` hold
+   *  whole records of `encoding` back to back, decompressed and checked in one
+   *  GPU launch in front of the aggregate; a record that does not decode makes
+   *  the answer false.
+   *  @throws std::invalid_argument as above, for an encoding the curve does not
+   *          offer, or a size that is not a multiple of the record length */
+  bool verify_coset_proofs(const std::vector<uint8_t>& commits, const std::vector<uint32_t>& commit_index,
+                           const std::vector<uint32_t>& cell_index, const std::vector<uint8_t>& proofs,
+                           const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
+                           bool bit_reversed, int encoding, bool check_subgroup = true);
   /** Extension: rebuild one erasure-coded blob from at least half of its cells
    *  (kzgx_recover_cells): the cells are those of create_coset_proofs(p, log2n,
    *  log2l, extended = true, bit_reversed), cell_index[k] the element number and

@@ -727,6 +727,74 @@ int kzgx_verify_cells_aggregate_checked_device(kzgx_ctx* ctx, const void* d_comm
                                                size_t count, unsigned log2n, unsigned log2l, int flags, int subgroup,
                                                void* d_ok, void* stream);
 
+/* ---- compressed points (extension) -------------------------------------------------------
+ * Commitments, proofs and published setups travel as compressed points: x and one
+ * bit of y.  These calls turn packed records into the canonical x || y limbs every
+ * other entry takes, and back, one lane per record in one launch; the root is
+ * y = (x^3 + b)^((p + 1) / 4) (both primes are 3 mod 4), accepted iff y^2 = x^3 + b
+ * (DESIGN.md "Compressed points").  No reference counterpart beyond the octet
+ * family of ECP_toOctet(..., true), which KZGX_ENC_SEC1 matches.
+ *  KZGX_ENC_ZCASH (BLS12-381 only; the ZCash / IETF encoding): a G1 record is 48
+ *   bytes, x big-endian; byte 0 carries 0x80 C (compressed, must be 1), 0x40 I
+ *   (infinity) and 0x20 S (sign: y > (p - 1) / 2).  I = 1 requires S = 0 and every
+ *   other bit zero.  x is the record with the three flag bits cleared and must be
+ *   < p.  A G2 record is 96 bytes, x.im || x.re, flags in byte 0; S = 1 means
+ *   y.im > (p - 1) / 2, or y.im = 0 and y.re > (p - 1) / 2.  BN254 has only two
+ *   spare bits: KZGX_ERR_ARG there.  Uncompressed records (C = 0) are not offered.
+ *  KZGX_ENC_SEC1 (both curves, G1 only): 1 + MODBYTES bytes (33 / 49), prefix
+ *   0x02 | (y mod 2), then x big-endian -- the compressed counterpart of the 0x04
+ *   octet.  Infinity is prefix 0x00 with an all-zero x (this library's convention,
+ *   INTEGRATION.md).  Every other prefix is invalid, 0x04 included.
+ *  Records are packed without padding; the limbs are W64 per coordinate, x || y
+ *   (G2: x.re, x.im, y.re, y.im).
+ *  Decompression: ok[k] = 1 iff record k is well-formed, x canonical and x^3 + b a
+ *   square, and, with subgroup != 0, the point lies in the order-r subgroup (the
+ *   tests of kzgx_g1_check_batch / kzgx_g2_check_batch, in the same launch).  A
+ *   record that fails decodes to infinity: all-zero limbs, out_is_inf = 1, ok = 0.
+ *   A valid identity record gives all-zero limbs, out_is_inf = 1, ok = 1.
+ *   out_is_inf may be NULL on the host entries.
+ *  Compression validates nothing: the sign comes from y as given.  Infinity (a set
+ *   flag or all-zero limbs; is_inf may be NULL) writes the identity record.
+ *  Device entries: device pointers (flags uint32), asynchronous on stream (NULL =
+ *   the context's); d_ok and d_all_ok as in kzgx_g1_check_batch_device (either may
+ *   be NULL, not both; *d_all_ok = AND of the flags, 1 for count == 0); d_out_is_inf
+ *   may be NULL.
+ *  Statuses: an unknown encoding, KZGX_ENC_ZCASH or any G2 call on BN254, a NULL
+ *   required pointer, more than KZGX_MSM_POINTS_MAX records: KZGX_ERR_ARG, raised
+ *   before any device work; count == 0: KZGX_OK.  No SRS is needed.
+ *  When it pays: README "Compressed points" and profiles/point_codec.json. */
+#define KZGX_ENC_ZCASH 0
+#define KZGX_ENC_SEC1 1
+/* record length in bytes, 0 if (curve, group 1 or 2, encoding) is not offered; host arithmetic, no device */
+size_t kzgx_point_bytes(int curve, int group, int encoding);
+int kzgx_g1_decompress_batch(kzgx_ctx* ctx, const uint8_t* bytes, size_t count, int encoding, int subgroup,
+                             uint64_t* out_xy, int* out_is_inf, int* ok);
+int kzgx_g1_decompress_batch_device(kzgx_ctx* ctx, const void* d_bytes, size_t count, int encoding, int subgroup,
+                                    void* d_out_xy, void* d_out_is_inf, void* d_ok, void* d_all_ok, void* stream);
+int kzgx_g1_compress_batch(kzgx_ctx* ctx, const uint64_t* xy, const int* is_inf, size_t count, int encoding,
+                           uint8_t* out);
+int kzgx_g1_compress_batch_device(kzgx_ctx* ctx, const void* d_xy, const void* d_is_inf, size_t count, int encoding,
+                                  void* d_out, void* stream);
+/* G2, KZGX_ENC_ZCASH, BLS12-381, host pointers (a setup's G2 half: a cold path) */
+int kzgx_g2_decompress_batch(kzgx_ctx* ctx, const uint8_t* bytes, size_t count, int subgroup, uint64_t* out_xy,
+                             int* out_is_inf, int* ok);
+int kzgx_g2_compress_batch(kzgx_ctx* ctx, const uint64_t* xy, const int* is_inf, size_t count, uint8_t* out);
+/* kzgx_verify_cells_aggregate_checked(_device) on compressed commitments and proofs:
+ * ONE decompress + check launch over both arrays, the unchanged aggregate on the
+ * recovered points (held in context workspace), and the device-side gate: a record
+ * that does not decode forces *ok = 0 like a point that fails the check.  Arguments,
+ * limits and statuses as the _checked forms, plus the encoding's. */
+int kzgx_verify_cells_aggregate_bytes(kzgx_ctx* ctx, const uint8_t* commits_bytes, size_t n_commits,
+                                      const uint32_t* commit_index, const uint32_t* cell_index,
+                                      const uint8_t* proofs_bytes, const uint64_t* ys, const uint64_t* challenges,
+                                      size_t count, unsigned log2n, unsigned log2l, int flags, int encoding,
+                                      int subgroup, int* ok);
+int kzgx_verify_cells_aggregate_bytes_device(kzgx_ctx* ctx, const void* d_commits_bytes, size_t n_commits,
+                                             const void* d_commit_index, const void* d_cell_index,
+                                             const void* d_proofs_bytes, const void* d_ys, const void* d_challenges,
+                                             size_t count, unsigned log2n, unsigned log2l, int flags, int encoding,
+                                             int subgroup, void* d_ok, void* stream);
+
 /* ---- cell recovery (extension) -----------------------------------------------------------
  * Rebuilds erasure-coded blobs from any half of their cells: the inverse of
  * kzgx_prove_cosets_batch(..., KZGX_PROVE_COSETS_EXTENDED), whose size-2n domain

@@ -72,6 +72,25 @@ assert BLS_BETA != 1 and pow(BLS_BETA, 3, BLS_P) == 1
 BLS_X2 = X * X  # the subgroup test's exponent: [x^2]P = (beta x, -y)
 assert (BLS_X2 * BLS_X2 - BLS_X2 + 1) == BLS_R
 
+# --------------------------------------------------------------------------
+# Compressed points (codec.hip).  Both primes are 3 mod 4, so a square a of Fp
+# has the root a^((p + 1) / 4); a is a square iff that power squares back to a.
+# In Fp2 = Fp[i] (p = 3 mod 4, complex method): a1 = a^((p - 3) / 4),
+# alpha = a1^2 a, x0 = a1 a; the root is i x0 when alpha = -1 and
+# (1 + alpha)^((p - 1) / 2) x0 otherwise.  (p - 1) / 2 is also the boundary of
+# the lexicographic sign: y is "large" when y > (p - 1) / 2.
+# --------------------------------------------------------------------------
+assert BN_P % 4 == 3 and BLS_P % 4 == 3
+
+
+def sqrt_consts(p, n):
+    return [
+        "  // compressed points: the Fp root's exponent, the sign boundary, the Fp2 root's first exponent",
+        "  static constexpr uint32_t SQRT_EXP[%d] = %s;  // (p + 1) / 4" % (n, arr((p + 1) // 4, n)),
+        "  static constexpr uint32_t HALF[%d] = %s;  // (p - 1) / 2" % (n, arr((p - 1) // 2, n)),
+        "  static constexpr uint32_t SQRT2_EXP[%d] = %s;  // (p - 3) / 4" % (n, arr((p - 3) // 4, n)),
+    ]
+
 
 def limbs(v, n):
     return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(n)]
@@ -403,6 +422,7 @@ def main():
         "  static constexpr uint32_t GX29[9] = %s;  // radix-2^29 Montgomery" % arr29(mont29(BN_P - 1, BN_P, 9), 9),
         "  static constexpr uint32_t GY29[9] = %s;" % arr29(mont29(1, BN_P, 9), 9),
         "  static constexpr bool COFACTOR_ONE = true;  // #E(Fp) = r: on the curve is in the subgroup",
+        *sqrt_consts(BN_P, 8),
         "};",
         "struct BLS12381G1 {",
         "  using Fp = BLS12381Fp;",
@@ -421,6 +441,7 @@ def main():
         "  static constexpr uint32_t BETA29[14] = %s;  // radix-2^29 Montgomery" % arr29(mont29(BLS_BETA, BLS_P, 14), 14),
         "  static constexpr uint64_t X2[2] = {0x%016xull, 0x%016xull};  // x^2" % (BLS_X2 & (2**64 - 1), BLS_X2 >> 64),
         "  static constexpr int X2_BITS = %d;" % BLS_X2.bit_length(),
+        *sqrt_consts(BLS_P, 12),
         "};",
         pairing_struct("BN254", 9, 8),
         pairing_struct("BLS12381", 14, 12),

@@ -233,6 +233,52 @@ std::vector<G1> ecp_deserialize_batch(const std::vector<std::vector<uint8_t>>& b
   return res;
 }
 
+// the record length of (the selected curve, G1 / G2, encoding), or invalid_argument
+size_t record_bytes(int group, int encoding) {
+  const size_t rb = kzgx_point_bytes(g_curve, group, encoding);
+  if (rb == 0) throw std::invalid_argument("compressed points: the curve does not offer this encoding");
+  return rb;
+}
+
+std::vector<uint8_t> g1_compressed(const G1& g, int encoding) {
+  std::vector<uint8_t> out(record_bytes(1, encoding));
+  const int nl = base_limbs();
+  std::vector<uint64_t> xy(2 * nl, 0);
+  for (int i = 0; i < nl; i++) {
+    xy[i] = g.x[i];
+    xy[nl + i] = g.y[i];
+  }
+  const int inf = g.inf;
+  check(kzgx_g1_compress_batch(default_ctx(), xy.data(), &inf, 1, encoding, out.data()), "kzgx_g1_compress_batch");
+  return out;
+}
+
+// every record of `packed` with ONE kzgx_g1_decompress_batch: the host splits nothing and computes nothing
+std::vector<G1> g1_decompress_packed(const std::vector<uint8_t>& packed, int encoding, bool check_subgroup,
+                                     std::vector<bool>* valid) {
+  const size_t rb = record_bytes(1, encoding);
+  if (packed.size() % rb) throw std::invalid_argument("compressed points: not a whole number of records");
+  const size_t m = packed.size() / rb;
+  const int nl = base_limbs();
+  std::vector<uint64_t> xy(2 * nl * m + 1, 0);
+  std::vector<int> inf(m + 1, 0), ok(m + 1, 0);
+  check(kzgx_g1_decompress_batch(default_ctx(), packed.data(), m, encoding, check_subgroup ? 1 : 0, xy.data(),
+                                 inf.data(), ok.data()),
+        "kzgx_g1_decompress_batch");
+  std::vector<G1> res(m);
+  if (valid) valid->assign(m, false);
+  for (size_t k = 0; k < m; k++) {
+    if (valid) (*valid)[k] = ok[k] != 0;
+    if (inf[k]) continue;
+    res[k].inf = false;
+    for (int i = 0; i < nl; i++) {
+      res[k].x[i] = xy[2 * nl * k + i];
+      res[k].y[i] = xy[2 * nl * k + nl + i];
+    }
+  }
+  return res;
+}
+
 }  // namespace
 
 // ---- Fr ---------------------------------------------------------------------
@@ -437,7 +483,49 @@ std::vector<proof> proof::deserialize_batch(const std::vector<std::vector<uint8_
   return res;
 }
 
+std::vector<uint8_t> commit::serialize_compressed(int encoding) { return g1_compressed(curve_point, encoding); }
+std::vector<uint8_t> proof::serialize_compressed(int encoding) { return g1_compressed(curve_point, encoding); }
+
+std::vector<commit> commit::deserialize_compressed_batch(const std::vector<uint8_t>& packed, int encoding,
+                                                         bool check_subgroup, std::vector<bool>* valid) {
+  std::vector<commit> res;
+  for (const G1& g : g1_decompress_packed(packed, encoding, check_subgroup, valid)) res.push_back(commit(g));
+  return res;
+}
+
+std::vector<proof> proof::deserialize_compressed_batch(const std::vector<uint8_t>& packed, int encoding,
+                                                       bool check_subgroup, std::vector<bool>* valid) {
+  std::vector<proof> res;
+  for (const G1& g : g1_decompress_packed(packed, encoding, check_subgroup, valid)) res.push_back(proof(g));
+  return res;
+}
+
 // ---- trusted_setup ----------------------------------------------------------
+trusted_setup trusted_setup::from_compressed(const std::vector<uint8_t>& g1, const std::vector<uint8_t>& g2,
+                                             bool check_subgroup) {
+  const size_t r1 = record_bytes(1, KZGX_ENC_ZCASH), r2 = record_bytes(2, KZGX_ENC_ZCASH);
+  if (g1.empty() || g2.empty() || g1.size() % r1 || g2.size() % r2)
+    throw std::invalid_argument("from_compressed: not a whole, positive number of records");
+  const size_t n1 = g1.size() / r1, n2 = g2.size() / r2;
+  const int nl = base_limbs(), sg = check_subgroup ? 1 : 0;
+  std::vector<uint64_t> xy(2 * nl * n1), xy2(4 * nl * n2);
+  std::vector<int> inf(std::max(n1, n2)), ok(std::max(n1, n2));
+  trusted_setup ts;
+  check(kzgx_create(&ts.ctx, g_curve, device()), "kzgx_create");  // ts's destructor frees it on a throw
+  check(kzgx_g1_decompress_batch(ts.ctx, g1.data(), n1, KZGX_ENC_ZCASH, sg, xy.data(), inf.data(), ok.data()),
+        "kzgx_g1_decompress_batch");
+  for (size_t i = 0; i < n1; i++)
+    if (!ok[i] || inf[i]) throw std::runtime_error("bad trusted setup file");
+  check(kzgx_g2_decompress_batch(ts.ctx, g2.data(), n2, sg, xy2.data(), inf.data(), ok.data()),
+        "kzgx_g2_decompress_batch");
+  for (size_t i = 0; i < n2; i++)
+    if (!ok[i] || inf[i]) throw std::logic_error("bad trusted setup file");
+  check(kzgx_load_srs_g1(ts.ctx, xy.data(), n1), "kzgx_load_srs_g1");
+  check(kzgx_load_srs_g2(ts.ctx, xy2.data(), n2), "kzgx_load_srs_g2");
+  ts.n = n1;
+  return ts;
+}
+
 trusted_setup::trusted_setup(int num_coeff) {
   if (num_coeff < 2) throw std::invalid_argument("num_coeff must be at least 2");
   // generate_random_BIG (util.cpp:62-76): 32 bytes from std::random_device, mod r
@@ -889,14 +977,13 @@ bool trusted_setup::verify_coset_proofs(std::vector<commit>& commits, const std:
                           check_subgroup);
 }
 
-bool trusted_setup::coset_aggregated(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
-                                     const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
-                                     const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
-                                     bool bit_reversed, bool checked, bool check_subgroup) {
-  const size_t m = proofs.size(), nc = commits.size();
+// the argument checks of the cell verifies (m cells of nc commitments); log2 of the cell size, 0 for m = 0
+static unsigned coset_cells_log2l(size_t m, size_t nc, const std::vector<uint32_t>& commit_index,
+                                  const std::vector<uint32_t>& cell_index, const std::vector<std::vector<Fr>>& values,
+                                  unsigned log2n, bool extended) {
   if (commit_index.size() != m || cell_index.size() != m || values.size() != m)
     throw std::invalid_argument("verify_coset_proofs: size mismatch");
-  if (m == 0) return true;
+  if (m == 0) return 0;
   const size_t l = values[0].size();
   if (l == 0 || (l & (l - 1))) throw std::invalid_argument("verify_coset_proofs: a cell's size is not a power of two");
   unsigned kl = 0;
@@ -911,6 +998,40 @@ bool trusted_setup::coset_aggregated(std::vector<commit>& commits, const std::ve
     if (commit_index[k] >= nc || cell_index[k] >= R)
       throw std::invalid_argument("verify_coset_proofs: index out of range");
   }
+  return kl;
+}
+
+bool trusted_setup::verify_coset_proofs(const std::vector<uint8_t>& commits, const std::vector<uint32_t>& commit_index,
+                                        const std::vector<uint32_t>& cell_index, const std::vector<uint8_t>& proofs,
+                                        const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
+                                        bool bit_reversed, int encoding, bool check_subgroup) {
+  const size_t rb = record_bytes(1, encoding);
+  if (commits.size() % rb || proofs.size() % rb)
+    throw std::invalid_argument("verify_coset_proofs: not a whole number of records");
+  const size_t m = proofs.size() / rb, nc = commits.size() / rb;
+  const unsigned kl = coset_cells_log2l(m, nc, commit_index, cell_index, values, log2n, extended);
+  if (m == 0) return true;
+  const size_t l = values[0].size();
+  std::vector<uint64_t> y(4 * m * l);
+  for (size_t k = 0; k < m; k++)
+    for (size_t j = 0; j < l; j++) std::memcpy(&y[4 * (k * l + j)], values[k][j].v.data(), 32);
+  const int flags = (extended ? KZGX_PROVE_COSETS_EXTENDED : 0) | (bit_reversed ? KZGX_NTT_BITREV : 0);
+  int ok = 0;
+  check(kzgx_verify_cells_aggregate_bytes(ctx, commits.data(), nc, commit_index.data(), cell_index.data(),
+                                          proofs.data(), y.data(), nullptr, m, log2n, kl, flags, encoding,
+                                          check_subgroup ? 1 : 0, &ok),
+        "kzgx_verify_cells_aggregate_bytes");
+  return ok != 0;
+}
+
+bool trusted_setup::coset_aggregated(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
+                                     const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
+                                     const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
+                                     bool bit_reversed, bool checked, bool check_subgroup) {
+  const size_t m = proofs.size(), nc = commits.size();
+  const unsigned kl = coset_cells_log2l(m, nc, commit_index, cell_index, values, log2n, extended);
+  if (m == 0) return true;
+  const size_t l = values[0].size();
   const int nl = base_limbs();
   std::vector<uint64_t> c(2 * nl * nc, 0), p(2 * nl * m, 0), y(4 * m * l);
   std::vector<int> ci(nc), pi(m);

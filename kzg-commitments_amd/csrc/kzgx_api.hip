@@ -2552,6 +2552,216 @@ int kzgx_verify_cells_aggregate_checked(kzgx_ctx* ctx, const uint64_t* commits_x
 
 }  // extern "C"
 
+// ---- compressed points (codec.hip) ------------------------------------------------------------
+namespace {
+// uint32 device flags -> the host's int flags (dst may be NULL)
+void flags_out(const std::vector<uint32_t>& f, size_t off, size_t count, int* dst) {
+  if (!dst) return;
+  for (size_t k = 0; k < count; k++) dst[k] = (int)f[off + k];
+}
+
+// the host-pointer decompression of either group: records in, limbs | infinity flags | ok flags out
+int decompress_host(kzgx_ctx* ctx, bool g2, const uint8_t* bytes, size_t count, int encoding, int subgroup,
+                    uint64_t* out_xy, int* out_is_inf, int* ok) {
+  KZGX_TRY(activate(ctx));
+  const size_t rb = kzgx::point_bytes(ctx->c.curve, g2 ? 2 : 1, encoding);
+  if (rb == 0) return KZGX_ERR_ARG;
+  if (count == 0) return KZGX_OK;
+  if (!bytes || !out_xy || !ok || count > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  const size_t pb = (g2 ? 2 : 1) * point_words(ctx) * 4;
+  void *d_b, *d_p, *d_f;
+  KZGX_TRY(stage(ctx, 0, count * rb, &d_b));
+  KZGX_TRY(stage(ctx, 1, count * pb, &d_p));
+  KZGX_TRY(stage(ctx, 2, count * 8, &d_f));
+  hipStream_t st = ctx->c.stream;
+  uint32_t* f = (uint32_t*)d_f;  // infinity flags | ok flags
+  KZGX_TRY_HIP(hipMemcpyAsync(d_b, bytes, count * rb, hipMemcpyHostToDevice, st));
+  if (g2)
+    KZGX_TRY(kzgx::g2_decompress(&ctx->c, (const uint8_t*)d_b, count, subgroup, (uint32_t*)d_p, f, f + count, st));
+  else
+    KZGX_TRY(kzgx::g1_decompress2(&ctx->c, (const uint8_t*)d_b, count, nullptr, 0, encoding, subgroup,
+                                  (uint32_t*)d_p, f, f + count, st));
+  std::vector<uint32_t> h(2 * count);
+  KZGX_TRY_HIP(hipMemcpyAsync(out_xy, d_p, count * pb, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(h.data(), d_f, count * 8, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  flags_out(h, 0, count, out_is_inf);
+  flags_out(h, count, count, ok);
+  return KZGX_OK;
+}
+
+int compress_host(kzgx_ctx* ctx, bool g2, const uint64_t* xy, const int* is_inf, size_t count, int encoding,
+                  uint8_t* out) {
+  KZGX_TRY(activate(ctx));
+  const size_t rb = kzgx::point_bytes(ctx->c.curve, g2 ? 2 : 1, encoding);
+  if (rb == 0) return KZGX_ERR_ARG;
+  if (count == 0) return KZGX_OK;
+  if (!xy || !out || count > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  const size_t pb = (g2 ? 2 : 1) * point_words(ctx) * 4;
+  void *d_p, *d_f, *d_b;
+  KZGX_TRY(stage(ctx, 0, count * pb, &d_p));
+  KZGX_TRY(stage(ctx, 1, count * 4, &d_f));
+  KZGX_TRY(stage(ctx, 2, count * rb, &d_b));
+  hipStream_t st = ctx->c.stream;
+  std::vector<uint32_t> f;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_p, xy, count * pb, hipMemcpyHostToDevice, st));
+  if (is_inf) {
+    f.resize(count);
+    for (size_t k = 0; k < count; k++) f[k] = (uint32_t)(is_inf[k] != 0);
+    KZGX_TRY_HIP(hipMemcpyAsync(d_f, f.data(), count * 4, hipMemcpyHostToDevice, st));
+  }
+  const uint32_t* d_inf = is_inf ? (const uint32_t*)d_f : nullptr;
+  if (g2)
+    KZGX_TRY(kzgx::g2_compress(&ctx->c, (const uint32_t*)d_p, d_inf, count, (uint8_t*)d_b, st));
+  else
+    KZGX_TRY(kzgx::g1_compress(&ctx->c, (const uint32_t*)d_p, d_inf, count, encoding, (uint8_t*)d_b, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(out, d_b, count * rb, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  return KZGX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t kzgx_point_bytes(int curve, int group, int encoding) { return kzgx::point_bytes(curve, group, encoding); }
+
+int kzgx_g1_decompress_batch(kzgx_ctx* ctx, const uint8_t* bytes, size_t count, int encoding, int subgroup,
+                             uint64_t* out_xy, int* out_is_inf, int* ok) {
+  return decompress_host(ctx, false, bytes, count, encoding, subgroup, out_xy, out_is_inf, ok);
+}
+
+int kzgx_g1_decompress_batch_device(kzgx_ctx* ctx, const void* d_bytes, size_t count, int encoding, int subgroup,
+                                    void* d_out_xy, void* d_out_is_inf, void* d_ok, void* d_all_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (kzgx::point_bytes(ctx->c.curve, 1, encoding) == 0) return KZGX_ERR_ARG;
+  if ((!d_ok && !d_all_ok) || (count > 0 && (!d_bytes || !d_out_xy)) || count > KZGX_MSM_POINTS_MAX)
+    return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  if (count == 0) {
+    if (d_all_ok) KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)d_all_ok, 1, 1, st));
+    return KZGX_OK;
+  }
+  uint32_t* flags = (uint32_t*)d_ok;
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  if (!flags) KZGX_TRY(chk_scratch(ctx, ws, count, &flags));
+  KZGX_TRY(kzgx::g1_decompress2(&ctx->c, (const uint8_t*)d_bytes, count, nullptr, 0, encoding, subgroup,
+                                (uint32_t*)d_out_xy, (uint32_t*)d_out_is_inf, flags, st));
+  if (d_all_ok) KZGX_TRY(kzgx::flags_and(flags, count, (uint32_t*)d_all_ok, st));
+  return KZGX_OK;
+}
+
+int kzgx_g1_compress_batch(kzgx_ctx* ctx, const uint64_t* xy, const int* is_inf, size_t count, int encoding,
+                           uint8_t* out) {
+  return compress_host(ctx, false, xy, is_inf, count, encoding, out);
+}
+
+int kzgx_g1_compress_batch_device(kzgx_ctx* ctx, const void* d_xy, const void* d_is_inf, size_t count, int encoding,
+                                  void* d_out, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (kzgx::point_bytes(ctx->c.curve, 1, encoding) == 0) return KZGX_ERR_ARG;
+  if ((count > 0 && (!d_xy || !d_out)) || count > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  return kzgx::g1_compress(&ctx->c, (const uint32_t*)d_xy, (const uint32_t*)d_is_inf, count, encoding,
+                           (uint8_t*)d_out, pick(ctx, stream));
+}
+
+int kzgx_g2_decompress_batch(kzgx_ctx* ctx, const uint8_t* bytes, size_t count, int subgroup, uint64_t* out_xy,
+                             int* out_is_inf, int* ok) {
+  return decompress_host(ctx, true, bytes, count, KZGX_ENC_ZCASH, subgroup, out_xy, out_is_inf, ok);
+}
+
+int kzgx_g2_compress_batch(kzgx_ctx* ctx, const uint64_t* xy, const int* is_inf, size_t count, uint8_t* out) {
+  return compress_host(ctx, true, xy, is_inf, count, KZGX_ENC_ZCASH, out);
+}
+
+int kzgx_verify_cells_aggregate_bytes_device(kzgx_ctx* ctx, const void* d_commits_bytes, size_t n_commits,
+                                             const void* d_commit_index, const void* d_cell_index,
+                                             const void* d_proofs_bytes, const void* d_ys, const void* d_challenges,
+                                             size_t count, unsigned log2n, unsigned log2l, int flags, int encoding,
+                                             int subgroup, void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (kzgx::point_bytes(ctx->c.curve, 1, encoding) == 0) return KZGX_ERR_ARG;
+  if (!d_ok || !d_challenges) return KZGX_ERR_ARG;
+  if (count > 0 && (!d_commit_index || !d_cell_index || !d_proofs_bytes || !d_ys || (n_commits > 0 && !d_commits_bytes)))
+    return KZGX_ERR_ARG;
+  CellsShape sh;
+  KZGX_TRY(cells_args(ctx, n_commits, count, log2n, log2l, flags, &sh));
+  hipStream_t st = pick(ctx, stream);
+  if (count == 0) {
+    KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)d_ok, 1, 1, st));
+    return KZGX_OK;
+  }
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const size_t np = n_commits + count, pw = point_words(ctx);
+  uint32_t* xy;  // the recovered commits | proofs, their infinity flags, their ok flags, the AND
+  KZGX_TRY(chk_scratch(ctx, ws, np * pw + 2 * np + 1, &xy));
+  uint32_t* inf = xy + np * pw;
+  uint32_t* okf = inf + np;
+  KZGX_TRY(kzgx::g1_decompress2(&ctx->c, (const uint8_t*)d_commits_bytes, n_commits, (const uint8_t*)d_proofs_bytes,
+                                count, encoding, subgroup, xy, inf, okf, st));
+  KZGX_TRY(kzgx::flags_and(okf, np, okf + np, st));
+  KZGX_TRY(kzgx_verify_cells_aggregate_device(ctx, xy, inf, n_commits, d_commit_index, d_cell_index,
+                                              xy + n_commits * pw, inf + n_commits, d_ys, d_challenges, count, log2n,
+                                              log2l, flags, d_ok, stream));
+  return kzgx::flag_gate((uint32_t*)d_ok, okf + np, st);
+}
+
+int kzgx_verify_cells_aggregate_bytes(kzgx_ctx* ctx, const uint8_t* commits_bytes, size_t n_commits,
+                                      const uint32_t* commit_index, const uint32_t* cell_index,
+                                      const uint8_t* proofs_bytes, const uint64_t* ys, const uint64_t* challenges,
+                                      size_t count, unsigned log2n, unsigned log2l, int flags, int encoding,
+                                      int subgroup, int* ok) {
+  KZGX_TRY(activate(ctx));
+  const size_t rb = kzgx::point_bytes(ctx->c.curve, 1, encoding);
+  if (rb == 0 || !ok) return KZGX_ERR_ARG;
+  if (count > 0 && (!commit_index || !cell_index || !proofs_bytes || !ys || (n_commits > 0 && !commits_bytes)))
+    return KZGX_ERR_ARG;
+  CellsShape sh;
+  KZGX_TRY(cells_args(ctx, n_commits, count, log2n, log2l, flags, &sh));
+  if (count == 0) {
+    *ok = 1;
+    return KZGX_OK;
+  }
+  for (size_t k = 0; k < count; k++)
+    if (commit_index[k] >= n_commits || (cell_index[k] >> sh.kR)) return KZGX_ERR_ARG;
+  // library-drawn challenges: independent 128-bit values, r_0 = 1 (as kzgx_verify_cells_aggregate)
+  std::vector<uint64_t> drawn;
+  if (!challenges) {
+    drawn.assign(count * 4, 0);
+    std::random_device rd;
+    for (size_t k = 0; k < count; k++)
+      for (int j = 0; j < 2; j++) drawn[4 * k + j] = ((uint64_t)rd() << 32) | (uint64_t)rd();
+    drawn[0] = 1;
+    drawn[1] = 0;
+    challenges = drawn.data();
+  }
+  const size_t cb = n_commits * rb, yb = count * sh.l * 32;
+  void *d_b, *d_s, *d_f;
+  KZGX_TRY(stage(ctx, 0, cb + count * rb, &d_b));  // commit records | proof records
+  KZGX_TRY(stage(ctx, 2, yb + count * 32, &d_s));
+  KZGX_TRY(stage(ctx, 3, 2 * count * 4 + 16, &d_f));  // commit_index | cell_index | ok
+  hipStream_t st = ctx->c.stream;
+  if (cb) KZGX_TRY_HIP(hipMemcpyAsync(d_b, commits_bytes, cb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync((char*)d_b + cb, proofs_bytes, count * rb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_s, ys, yb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync((char*)d_s + yb, challenges, count * 32, hipMemcpyHostToDevice, st));
+  uint32_t* f = (uint32_t*)d_f;
+  KZGX_TRY_HIP(hipMemcpyAsync(f, commit_index, count * 4, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(f + count, cell_index, count * 4, hipMemcpyHostToDevice, st));
+  uint32_t* d_ok = f + 2 * count;
+  KZGX_TRY(kzgx_verify_cells_aggregate_bytes_device(ctx, d_b, n_commits, f, f + count, (char*)d_b + cb, d_s,
+                                                    (char*)d_s + yb, count, log2n, log2l, flags, encoding, subgroup,
+                                                    d_ok, nullptr));
+  uint32_t v = 0;
+  KZGX_TRY_HIP(hipMemcpyAsync(&v, d_ok, 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  *ok = v ? 1 : 0;
+  return KZGX_OK;
+}
+
+}  // extern "C"
+
 // ---- cell recovery ----------------------------------------------------------------------------
 namespace {
 // the argument checks shared by the four entries (proofs: also the SRS the openings need)

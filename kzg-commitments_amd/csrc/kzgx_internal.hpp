@@ -530,6 +530,19 @@ int g2_check(Ctx* ctx, const uint32_t* d_xy, const uint32_t* d_inf, size_t count
 // *d_all = AND of count flags (1 when count == 0); *d_ok = *d_ok && *d_gate
 int flags_and(const uint32_t* d_flags, size_t count, uint32_t* d_all, hipStream_t st);
 int flag_gate(uint32_t* d_ok, const uint32_t* d_gate, hipStream_t st);
+// compressed points (codec.hip).  point_bytes: the record length, 0 when
+// (curve, group, encoding) is not offered.  g1_decompress2: two packed record
+// arrays in one launch (count1 may be 0), results for count0 + count1 points in
+// that order: canonical x || y words, infinity flags (may be null), ok flags.
+// The G2 pair is BLS12-381 / KZGX_ENC_ZCASH only.
+size_t point_bytes(int curve, int group, int encoding);
+int g1_decompress2(Ctx* ctx, const uint8_t* d_b0, size_t count0, const uint8_t* d_b1, size_t count1, int encoding,
+                   int subgroup, uint32_t* d_xy, uint32_t* d_inf, uint32_t* d_ok, hipStream_t st);
+int g1_compress(Ctx* ctx, const uint32_t* d_xy, const uint32_t* d_inf, size_t count, int encoding, uint8_t* d_out,
+                hipStream_t st);
+int g2_decompress(Ctx* ctx, const uint8_t* d_b, size_t count, int subgroup, uint32_t* d_xy, uint32_t* d_inf,
+                  uint32_t* d_ok, hipStream_t st);
+int g2_compress(Ctx* ctx, const uint32_t* d_xy, const uint32_t* d_inf, size_t count, uint8_t* d_out, hipStream_t st);
 int g1_sub(Ctx* ctx, const uint32_t* d_a, const uint32_t* d_a_inf, const uint32_t* d_b, const uint32_t* d_b_inf,
            uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st);
 

@@ -31,33 +31,9 @@
 
 #include "kzgx_internal.hpp"
 #include "kzgx_setup.hpp"
-#include "tower.hpp"
+#include "point_check.hpp"
 
 namespace kzgx {
-
-// canonical and on the curve, k_g1_validate's test; a: the point in Montgomery form
-template <class C>
-KZGX_DEV bool g1_canonical_on_curve(const uint32_t* __restrict__ xy, Affine<C>& a) {
-  using F = typename C::Fp29;
-  constexpr int N = C::Fp::N;
-  bool lt = true;
-  for (int c = 0; c < 2; c++) {
-    int cmp = 0;  // coordinate vs modulus, most significant word first
-    for (int i = N - 1; i >= 0 && cmp == 0; i--) {
-      const uint32_t w = xy[c * N + i], m = C::Fp::P[i];
-      cmp = w < m ? -1 : (w > m ? 1 : 0);
-    }
-    lt = lt && cmp < 0;
-  }
-  const bool finite = affine_from_canonical<C>(xy, a);
-  uint32_t bw[N];
-  for (int i = 0; i < N; i++) bw[i] = i == 0 ? C::BSMALL : 0u;
-  const F29<F> b = f29_to_mont<F>(f29_from_words<F, N>(bw));
-  const F29<F> y2 = f29_sqr<F>(a.y);
-  const F29<F> x3 = f29_mul<F>(f29_sqr<F>(a.x), a.x);
-  const F29<F> d = f29_sub<F>(y2, f29_add<F>(x3, b), F::P4);  // < 6m
-  return lt && finite && f29_is_zero<F>(d);
-}
 
 // Two arrays in one launch (count1 may be 0): lane k checks point k of the
 // first array for k < count0, else point k - count0 of the second; ok holds
@@ -91,16 +67,7 @@ __global__ __launch_bounds__(64) void k_g1_check(const uint32_t* __restrict__ xy
         a.x = f29_const<F>(C::GX29);
         a.y = f29_const<F>(C::GY29);
       }
-      Xyzz<C> acc = xyzz_from_affine<C>(a);  // the top bit of x^2
-      for (int b = C::X2_BITS - 2; b >= 0; b--) {
-        acc = xyzz_dbl<C>(acc);
-        if ((C::X2[b >> 6] >> (b & 63)) & 1ull) acc = xyzz_add_affine<C>(acc, a);
-      }
-      // [x^2]P == (beta x, -y): X = beta x ZZ and Y + y ZZZ = 0, ZZ != 0
-      const F29<F> bx = f29_mul<F>(f29_const<F>(C::BETA29), a.x);                       // < 2m
-      const F29<F> dx = f29_sub<F>(acc.X, f29_mul<F>(bx, acc.ZZ), F::P2);               // < 10m
-      const F29<F> dy = f29_add<F>(acc.Y, f29_mul<F>(a.y, acc.ZZZ));                    // < 6m
-      member = !xyzz_is_inf<C>(acc) && f29_is_zero<F>(dx) && f29_is_zero<F>(dy);
+      member = g1_in_subgroup<C>(a);
     }
   }
   ok[k] = (is_inf || (on && member)) ? 1u : 0u;
@@ -127,13 +94,7 @@ __global__ __launch_bounds__(64) void k_g2_check(const uint32_t* __restrict__ xy
       q.x = f2_const<C>(P::G2X);
       q.y = f2_const<C>(P::G2Y);
     }
-    using FR = typename C::Fr;
-    G2J<C> acc = g2_from_affine<C>(q);  // the top bit of r
-    for (int b = FR::BITS - 2; b >= 0; b--) {
-      acc = g2_dbl<C>(acc);
-      if ((FR::P[b >> 5] >> (b & 31)) & 1u) acc = g2_add_mixed<C>(acc, q);
-    }
-    member = g2_is_inf<C>(acc);
+    member = g2_in_subgroup<C>(q);
   }
   ok[k] = (is_inf || (on && member)) ? 1u : 0u;
 }

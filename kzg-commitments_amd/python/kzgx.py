@@ -46,6 +46,9 @@ EXPORTS = [
     "kzgx_verify_cells_aggregate_checked_device",
     "kzgx_recover_cells", "kzgx_recover_cells_device", "kzgx_recover_cells_and_proofs",
     "kzgx_recover_cells_and_proofs_device",
+    "kzgx_point_bytes", "kzgx_g1_decompress_batch", "kzgx_g1_decompress_batch_device", "kzgx_g1_compress_batch",
+    "kzgx_g1_compress_batch_device", "kzgx_g2_decompress_batch", "kzgx_g2_compress_batch",
+    "kzgx_verify_cells_aggregate_bytes", "kzgx_verify_cells_aggregate_bytes_device",
 ]
 
 
@@ -71,11 +74,15 @@ PROVE_COSETS_EXTENDED = _header_define("KZGX_PROVE_COSETS_EXTENDED")
 # cell recovery: the most cells per blob (log2), and the scalars per internal chunk of blobs
 RECOVER_MAX_LOG2_CELLS = _header_define("KZGX_RECOVER_MAX_LOG2_CELLS")
 RECOVER_CHUNK_SCALARS = _header_define("KZGX_RECOVER_CHUNK_SCALARS")
+# compressed points: the ZCash / IETF BLS12-381 encoding, and SEC1 (0x02 | parity, then x)
+ENC_ZCASH = _header_define("KZGX_ENC_ZCASH")
+ENC_SEC1 = _header_define("KZGX_ENC_SEC1")
 
 _lib = None
 u64p = ctypes.POINTER(ctypes.c_uint64)
 intp = ctypes.POINTER(ctypes.c_int)
 u32p = ctypes.POINTER(ctypes.c_uint32)
+u8p = ctypes.POINTER(ctypes.c_uint8)
 vp = ctypes.c_void_p
 sz = ctypes.c_size_t
 
@@ -225,6 +232,20 @@ def lib():
             "kzgx_recover_cells_and_proofs_device": (ctypes.c_int, [vp, vp, vp, vp, sz, sz, ctypes.c_uint,
                                                                     ctypes.c_uint, ctypes.c_int, vp, vp, vp, vp, vp,
                                                                     vp]),
+            "kzgx_point_bytes": (sz, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+            "kzgx_g1_decompress_batch": (ctypes.c_int, [vp, u8p, sz, ctypes.c_int, ctypes.c_int, u64p, intp, intp]),
+            "kzgx_g1_decompress_batch_device": (ctypes.c_int, [vp, vp, sz, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp,
+                                                               vp]),
+            "kzgx_g1_compress_batch": (ctypes.c_int, [vp, u64p, intp, sz, ctypes.c_int, u8p]),
+            "kzgx_g1_compress_batch_device": (ctypes.c_int, [vp, vp, vp, sz, ctypes.c_int, vp, vp]),
+            "kzgx_g2_decompress_batch": (ctypes.c_int, [vp, u8p, sz, ctypes.c_int, u64p, intp, intp]),
+            "kzgx_g2_compress_batch": (ctypes.c_int, [vp, u64p, intp, sz, u8p]),
+            "kzgx_verify_cells_aggregate_bytes": (ctypes.c_int, [vp, u8p, sz, u32p, u32p, u8p, u64p, u64p, sz,
+                                                                 ctypes.c_uint, ctypes.c_uint, ctypes.c_int,
+                                                                 ctypes.c_int, ctypes.c_int, intp]),
+            "kzgx_verify_cells_aggregate_bytes_device": (ctypes.c_int, [vp, vp, sz, vp, vp, vp, vp, vp, sz,
+                                                                        ctypes.c_uint, ctypes.c_uint, ctypes.c_int,
+                                                                        ctypes.c_int, ctypes.c_int, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -289,6 +310,12 @@ def fixed_base_bytes(curve: str, c: int, n_points: int) -> int:
 def ntt_max_log2(curve: str) -> int:
     """kzgx_ntt_max_log2: the largest log2 n of the curve's NTT (host arithmetic, no device)"""
     return lib().kzgx_ntt_max_log2(CURVES[curve])
+
+
+def point_bytes(curve: str, group: int, encoding: int) -> int:
+    """kzgx_point_bytes: the record length of a compressed point, 0 if the combination is not offered
+    (host arithmetic, no device)"""
+    return int(lib().kzgx_point_bytes(CURVES[curve], group, encoding))
 
 
 def domain_root(curve: str, log2n: int) -> int:
@@ -1010,6 +1037,108 @@ class Context:
             self.h, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index, d_proofs, d_proof_inf, d_ys,
             d_challenges, count, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), int(bool(subgroup)), d_ok,
             stream), "kzgx_verify_cells_aggregate_checked_device")
+
+    # ---- compressed points ----
+    def _records(self, data, rb) -> np.ndarray:
+        b = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else \
+            np.ascontiguousarray(data, dtype=np.uint8)
+        b = np.ascontiguousarray(b).reshape(-1)
+        assert rb and b.shape[0] % rb == 0
+        return b
+
+    def _decompress(self, fn, name, group, data, encoding, extra):
+        rb = point_bytes(self.curve, group, encoding)
+        if rb == 0:  # not offered: the library's own status
+            _chk(fn(self.h, None, 0, *extra, None, None, None), name)
+        b = self._records(data, rb)
+        n = b.shape[0] // rb
+        out = np.zeros((n, 2 * group * self.w64), dtype=np.uint64)
+        inf = np.zeros(n, dtype=np.int32)
+        ok = np.zeros(n, dtype=np.int32)
+        _chk(fn(self.h, b.ctypes.data_as(u8p) if n else None, n, *extra, _p(out), inf.ctypes.data_as(intp),
+                ok.ctypes.data_as(intp)), name)
+        return out, inf.astype(bool), ok.astype(bool)
+
+    def g1_decompress(self, data, encoding=ENC_ZCASH, subgroup: bool = False):
+        """kzgx_g1_decompress_batch: packed records -> (points (n, 2 w64), is_inf (n,), ok (n,)); a record that
+        does not decode gives all-zero limbs, is_inf and not ok."""
+        return self._decompress(lib().kzgx_g1_decompress_batch, "kzgx_g1_decompress_batch", 1, data, encoding,
+                                (encoding, int(bool(subgroup))))
+
+    def g2_decompress(self, data, subgroup: bool = False):
+        """kzgx_g2_decompress_batch (ZCash encoding): packed 96-byte records -> (points (n, 4 w64), is_inf, ok)."""
+        return self._decompress(lib().kzgx_g2_decompress_batch, "kzgx_g2_decompress_batch", 2, data, ENC_ZCASH,
+                                (int(bool(subgroup)),))
+
+    def g1_decompress_device(self, d_bytes, count, encoding, subgroup, d_out_xy, d_out_inf, d_ok, d_all_ok,
+                             stream=None):
+        """kzgx_g1_decompress_batch_device: device pointers (flags uint32; d_out_inf, and one of d_ok / d_all_ok,
+        may be None), enqueued on stream."""
+        _chk(lib().kzgx_g1_decompress_batch_device(self.h, d_bytes, count, encoding, int(bool(subgroup)), d_out_xy,
+                                                   d_out_inf, d_ok, d_all_ok, stream),
+             "kzgx_g1_decompress_batch_device")
+
+    def _compress(self, fn, name, group, pts, inf, encoding, extra):
+        rb = point_bytes(self.curve, group, encoding)
+        if rb == 0:  # not offered: the library's own status
+            _chk(fn(self.h, None, None, 0, *extra, None), name)
+        xy = np.ascontiguousarray(pts, dtype=np.uint64).reshape(-1, 2 * group * self.w64)
+        n = xy.shape[0]
+        f = None if inf is None else np.ascontiguousarray(inf, dtype=np.int32)
+        assert f is None or f.shape[0] == n
+        out = np.zeros(n * rb, dtype=np.uint8)
+        _chk(fn(self.h, _p(xy) if n else None, None if f is None else f.ctypes.data_as(intp), n, *extra,
+                out.ctypes.data_as(u8p)), name)
+        return out.tobytes()
+
+    def g1_compress(self, pts, inf=None, encoding=ENC_ZCASH) -> bytes:
+        """kzgx_g1_compress_batch: canonical limbs (+ infinity flags) -> packed records; validates nothing."""
+        return self._compress(lib().kzgx_g1_compress_batch, "kzgx_g1_compress_batch", 1, pts, inf, encoding,
+                              (encoding,))
+
+    def g2_compress(self, pts, inf=None) -> bytes:
+        """kzgx_g2_compress_batch (ZCash encoding)."""
+        return self._compress(lib().kzgx_g2_compress_batch, "kzgx_g2_compress_batch", 2, pts, inf, ENC_ZCASH, ())
+
+    def g1_compress_device(self, d_xy, d_inf, count, encoding, d_out, stream=None):
+        """kzgx_g1_compress_batch_device: device pointers, enqueued on stream."""
+        _chk(lib().kzgx_g1_compress_batch_device(self.h, d_xy, d_inf, count, encoding, d_out, stream),
+             "kzgx_g1_compress_batch_device")
+
+    def verify_cells_aggregate_bytes(self, commits, commit_index, cell_index, proofs, ys, log2n, challenges=None,
+                                     encoding=ENC_ZCASH, extended=False, bitrev=False, subgroup: bool = False) -> bool:
+        """kzgx_verify_cells_aggregate_bytes: verify_cells_aggregate_checked on packed compressed commitments
+        and proofs (bytes or uint8 arrays); a record that does not decode gives False."""
+        rb = point_bytes(self.curve, 1, encoding)
+        if rb == 0:  # not offered: the library's own status
+            _chk(lib().kzgx_verify_cells_aggregate_bytes(self.h, None, 0, None, None, None, None, None, 0, log2n, 0,
+                                                         0, encoding, 0, None), "kzgx_verify_cells_aggregate_bytes")
+        c, p = self._records(commits, rb), self._records(proofs, rb)
+        nc, n = c.shape[0] // rb, p.shape[0] // rb
+        y = np.ascontiguousarray(ys, dtype=np.uint64)
+        assert y.ndim >= 2 and y.shape[-1] == 4
+        log2l = _log2_exact(y.shape[-2])
+        y = y.reshape(-1, y.shape[-2], 4)
+        ci = np.ascontiguousarray(commit_index, dtype=np.uint32).reshape(-1)
+        ki = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)
+        r = None if challenges is None or not n else as_scalars(challenges)
+        assert y.shape[0] == n and ci.shape[0] == n and ki.shape[0] == n and (r is None or r.shape[0] == n)
+        ok = ctypes.c_int(0)
+        _chk(lib().kzgx_verify_cells_aggregate_bytes(
+            self.h, c.ctypes.data_as(u8p) if nc else None, nc, ci.ctypes.data_as(u32p) if n else None,
+            ki.ctypes.data_as(u32p) if n else None, p.ctypes.data_as(u8p) if n else None, _p(y) if n else None,
+            None if r is None else _p(r), n, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), encoding,
+            int(bool(subgroup)), ctypes.byref(ok)), "kzgx_verify_cells_aggregate_bytes")
+        return bool(ok.value)
+
+    def verify_cells_aggregate_bytes_device(self, d_commits, n_commits, d_commit_index, d_cell_index, d_proofs, d_ys,
+                                            d_challenges, count, log2n, log2l, encoding, subgroup, d_ok,
+                                            extended=False, bitrev=False, stream=None):
+        """kzgx_verify_cells_aggregate_bytes_device: the same with device pointers, still asynchronous."""
+        _chk(lib().kzgx_verify_cells_aggregate_bytes_device(
+            self.h, d_commits, n_commits, d_commit_index, d_cell_index, d_proofs, d_ys, d_challenges, count, log2n,
+            log2l, _cosets_flags(extended, bitrev=bitrev), encoding, int(bool(subgroup)), d_ok, stream),
+            "kzgx_verify_cells_aggregate_bytes_device")
 
     # ---- cell recovery ----
     def _recover_host(self, proofs, blob_index, cell_index, ys, n_blobs, log2n, extended, bitrev, want_y,

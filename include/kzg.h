@@ -196,7 +196,7 @@ class trusted_setup {
   bool coset_aggregated(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
                         const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
                         const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended, bool bit_reversed,
-                        bool checked, bool check_subgroup);
+                        bool checked, bool check_subgroup, std::vector<bool>* each = nullptr);
   std::vector<Fr> recovered(const std::vector<uint32_t>& cell_index, const std::vector<std::vector<Fr>>& values,
                             unsigned log2n, bool bit_reversed, std::vector<proof>* proofs);
 
@@ -318,8 +318,8 @@ class trusted_setup {
    *  number of create_coset_proofs(..., bit_reversed = true) and values[k] the
    *  matching chunk of the bit-reversed evaluation array, as they come.  Each
    *  commitment is passed once.  True iff every cell verifies (false-accept
-   *  probability <= 2^-128); on false, verify_proof per cell (over the points
-   *  kzgx_coset_points lists) says which.  An empty batch is true.  Needs
+   *  probability <= 2^-128); on false, verify_coset_proofs_each says which.
+   *  An empty batch is true.  Needs
    *  only 2^log2l G1 and 2^log2l + 1 G2 setup points, whatever log2n.
    *  @throws std::invalid_argument on mismatched sizes, values whose length is
    *          not one power of two shared by all cells, an index out of range,
@@ -336,6 +336,25 @@ class trusted_setup {
                            const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
                            const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
                            bool bit_reversed, bool check_subgroup);
+  /** Extension: the same batch, one verdict per cell (kzgx_verify_cells_each):
+   *  element k is what verify_proof answers for cell k over the points
+   *  kzgx_coset_points lists -- exact and deterministic, no challenges, so
+   *  errors that would cancel in the aggregate are each reported.  One batched
+   *  GPU pipeline for the whole list, not a call per cell.  An empty batch
+   *  gives an empty vector.  Setup points and exceptions as
+   *  verify_coset_proofs. */
+  std::vector<bool> verify_coset_proofs_each(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
+                                             const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
+                                             const std::vector<std::vector<Fr>>& values, unsigned log2n,
+                                             bool extended = false, bool bit_reversed = false);
+  /** Extension: the same behind a validation of every commit and proof
+   *  (kzgx_verify_cells_each_checked): a cell whose proof or commitment is not
+   *  canonical, not on the curve or, with check_subgroup, outside the
+   *  prime-order subgroup is false; the other cells keep their verdicts. */
+  std::vector<bool> verify_coset_proofs_each(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
+                                             const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
+                                             const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
+                                             bool bit_reversed, bool check_subgroup);
   /** Extension: the checked form on compressed commitments and proofs as they
    *  travel (kzgx_verify_cells_aggregate_bytes): `commits` and `proofs` hold
    *  whole records of `encoding` back to back, decompressed and checked in one

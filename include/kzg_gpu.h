@@ -25,7 +25,8 @@
  * openings of a polynomial on its size-n domain in Theta(n log n) group operations;
  * kzgx_prove_cosets_*, kzgx_coset_points: one opening per coset (cell) of that
  * domain or of the twice larger one, all cosets at once;
- * kzgx_verify_cells_aggregate*: one pairing check for many such cells.
+ * kzgx_verify_cells_aggregate*: one pairing check for many such cells;
+ * kzgx_verify_cells_each*: one verdict per cell of such a batch.
  *
  * Conventions
  *   - plain pointers and sizes only; no torch / HIP types in signatures
@@ -671,8 +672,8 @@ int kzgx_prove_cosets_batch_device(kzgx_ctx* ctx, const void* d_in, unsigned log
  *   The equivalence with the AND of the per-cell kzgx_verify_proof calls is
  *   kzgx_verify_aggregate's: equal when every cell is valid, and whenever exactly
  *   one is invalid under nonzero challenges; errors can cancel under challenges
- *   the prover predicts.  Which cell failed is not reported: kzgx_verify_proof per
- *   cell says.
+ *   the prover predicts.  Which cell failed is not reported here:
+ *   kzgx_verify_cells_each (below) gives one verdict per cell.
  *  Setup: a G1 SRS of at least l points with G1[t] = [tau^t]G for t < l, and a G2
  *   setup of at least l + 1 points.  The call never touches n SRS points, so
  *   2^log2n may exceed the installed SRS: a verifier of the data-availability
@@ -726,6 +727,82 @@ int kzgx_verify_cells_aggregate_checked_device(kzgx_ctx* ctx, const void* d_comm
                                                const void* d_proof_inf, const void* d_ys, const void* d_challenges,
                                                size_t count, unsigned log2n, unsigned log2l, int flags, int subgroup,
                                                void* d_ok, void* stream);
+
+/* ---- per-cell verdicts (extension) -------------------------------------------------------
+ * kzgx_verify_cells_each*: the same batch, one answer per cell.  With the notation
+ * above, for every cell k
+ *   ok[k] = e(pi_k, G2[l]) == e(C_(c_k) - [I_k(tau)]G1 + [a_(i_k)]pi_k, G2[0])
+ * -- the boolean of kzgx_verify_proof(C_(c_k), pi_k, xs = kzgx_coset_points(...,
+ * cell_index[k]), ys = y_k), with one exception: kzgx_verify_proof answers 0 when
+ * npoints >= the G1 SRS's size, this entry needs l G1 and l + 1 G2 points like the
+ * aggregate and answers the equation.  There are no challenges: the answer is
+ * deterministic and exact per cell, and errors that cancel in the aggregate under
+ * equal challenges are reported as separate failures.  Use it after the aggregate
+ * said 0, or instead of it, to find the cells to drop (kzgx_recover_cells takes the
+ * rest) and their sender.
+ *  Arguments: kzgx_verify_cells_aggregate's without `challenges`; ok: count entries.
+ *  Pipeline, in chunks of at most KZGX_VERIFY_CELLS_EACH_CHUNK cells and
+ *   KZGX_VERIFY_CELLS_EACH_CHUNK_VALUES values (kzgx_set_verify_cells_chunk(ctx,
+ *   cells) overrides the former, 0 = default, at most 65535: a test knob): the
+ *   size-l inverse NTTs, a twiddle per coefficient (I_k), one batched fixed-base
+ *   MSM of the chunk's interpolants over G1[0..l) (the context's table settings pick
+ *   its path as for kzgx_msm_g1_batch), one lane per cell for C - [I(tau)]G1, and
+ *   the two kernels of kzgx_verify_single_batch_device on (C', pi, z = a, y = 0)
+ *   with G2[l] in G2[1]'s place -- the wave-per-opening one for count <=
+ *   kzgx_set_verify_wave_max's bound, else the lane-per-opening one; both give the
+ *   same booleans.  The workspace per stream is bounded by the chunk, not by count.
+ *   The first call for a coset size l stages G2[0] || G2[l] and, on the wave path,
+ *   builds their line tables (one stream synchronisation, as the first
+ *   kzgx_verify_single_batch_device after a setup); both are dropped with the setup.
+ *  The _checked forms first run the G1 check of kzgx_g1_check_batch over the
+ *   commitments and the proofs and force ok[k] = 0 for a cell whose proof or
+ *   commitment fails it: a bad commitment zeroes every cell that names it and no
+ *   other.
+ *  Device entries: device pointers (indices, infinity flags and d_ok uint32, count
+ *   words), asynchronous on stream, no host read-back.  An index out of range
+ *   (commit_index >= n_commits, cell_index >= R) reads nothing out of bounds and
+ *   gives d_ok[k] = 0 for that cell only.
+ *  When it pays (BLS12-381, MI355X, profiles/verify_cells_each.json, DESIGN.md
+ *   "Per-cell verdicts"): at (12, 6) extended, bit-reversed, a device call takes
+ *   7.9 ms for 128 cells, 16.8 ms for 1024 and 109.0 ms for 8192 (75k cells/s),
+ *   against 4.03 ms per kzgx_verify_proof call of one cell (host wall clock, 64
+ *   calls timed and scaled): 516, 4119 and 33012 ms, x66, x246 and x303.  One
+ *   cell: 1.9 against 4.0 ms; two cells are a TIE with the separate calls (7.4
+ *   against 7.3 ms, spreads overlapping).  It LOSES to
+ *   kzgx_verify_cells_aggregate_device, which pays one pairing product whatever
+ *   the count (9.9 to 10.3 ms), from about 300 cells on (interpolated): x0.80 at
+ *   128 cells, x1.62 at 1024, x10.7 at 8192 -- run the aggregate first and this
+ *   call only on a batch it refused.  The count pairing products are the call:
+ *   90% of it at 128 cells, 97% at 8192 (106 ms); the batched MSM takes 0.6 to
+ *   3.4 ms with the default table (1.1 to 22.5 ms without), the inverse NTTs and
+ *   twiddles under 0.08 ms, the subtraction 0.13 ms.  At 8192 cells the default
+ *   bound picks the SLOWER pairing kernel: the lane-per-opening one takes 75.6 ms
+ *   there (x1.44; 68 ms at any count below about 4000, where it loses); the two
+ *   cross near 5000 cells, and kzgx_set_verify_wave_max moves the switch.  The
+ *   lane kernel also still walks the 256 doublings of [y]G for y = 0.
+ *  Statuses: those of kzgx_verify_cells_aggregate (the same argument, limit and
+ *   setup checks, and on the host entries KZGX_ERR_ARG for an index out of range);
+ *   count == 0: KZGX_OK, nothing is written (n_commits may then be 0). */
+#define KZGX_VERIFY_CELLS_EACH_CHUNK 16384
+#define KZGX_VERIFY_CELLS_EACH_CHUNK_VALUES ((size_t)1 << 21)
+int kzgx_verify_cells_each(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                           const uint32_t* commit_index, const uint32_t* cell_index, const uint64_t* proofs_xy,
+                           const int* proof_inf, const uint64_t* ys, size_t count, unsigned log2n, unsigned log2l,
+                           int flags, int* ok);
+int kzgx_verify_cells_each_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, size_t n_commits,
+                                  const void* d_commit_index, const void* d_cell_index, const void* d_proofs,
+                                  const void* d_proof_inf, const void* d_ys, size_t count, unsigned log2n,
+                                  unsigned log2l, int flags, void* d_ok, void* stream);
+int kzgx_verify_cells_each_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf,
+                                   size_t n_commits, const uint32_t* commit_index, const uint32_t* cell_index,
+                                   const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* ys, size_t count,
+                                   unsigned log2n, unsigned log2l, int flags, int subgroup, int* ok);
+int kzgx_verify_cells_each_checked_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                          size_t n_commits, const void* d_commit_index, const void* d_cell_index,
+                                          const void* d_proofs, const void* d_proof_inf, const void* d_ys,
+                                          size_t count, unsigned log2n, unsigned log2l, int flags, int subgroup,
+                                          void* d_ok, void* stream);
+int kzgx_set_verify_cells_chunk(kzgx_ctx* ctx, size_t cells);
 
 /* ---- compressed points (extension) -------------------------------------------------------
  * Commitments, proofs and published setups travel as compressed points: x and one

@@ -977,6 +977,30 @@ bool trusted_setup::verify_coset_proofs(std::vector<commit>& commits, const std:
                           check_subgroup);
 }
 
+std::vector<bool> trusted_setup::verify_coset_proofs_each(std::vector<commit>& commits,
+                                                          const std::vector<uint32_t>& commit_index,
+                                                          const std::vector<uint32_t>& cell_index,
+                                                          std::vector<proof>& proofs,
+                                                          const std::vector<std::vector<Fr>>& values, unsigned log2n,
+                                                          bool extended, bool bit_reversed) {
+  std::vector<bool> each;
+  coset_aggregated(commits, commit_index, cell_index, proofs, values, log2n, extended, bit_reversed, false, false,
+                   &each);
+  return each;
+}
+
+std::vector<bool> trusted_setup::verify_coset_proofs_each(std::vector<commit>& commits,
+                                                          const std::vector<uint32_t>& commit_index,
+                                                          const std::vector<uint32_t>& cell_index,
+                                                          std::vector<proof>& proofs,
+                                                          const std::vector<std::vector<Fr>>& values, unsigned log2n,
+                                                          bool extended, bool bit_reversed, bool check_subgroup) {
+  std::vector<bool> each;
+  coset_aggregated(commits, commit_index, cell_index, proofs, values, log2n, extended, bit_reversed, true,
+                   check_subgroup, &each);
+  return each;
+}
+
 // the argument checks of the cell verifies (m cells of nc commitments); log2 of the cell size, 0 for m = 0
 static unsigned coset_cells_log2l(size_t m, size_t nc, const std::vector<uint32_t>& commit_index,
                                   const std::vector<uint32_t>& cell_index, const std::vector<std::vector<Fr>>& values,
@@ -1027,9 +1051,12 @@ bool trusted_setup::verify_coset_proofs(const std::vector<uint8_t>& commits, con
 bool trusted_setup::coset_aggregated(std::vector<commit>& commits, const std::vector<uint32_t>& commit_index,
                                      const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
                                      const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended,
-                                     bool bit_reversed, bool checked, bool check_subgroup) {
+                                     bool bit_reversed, bool checked, bool check_subgroup,
+                                     std::vector<bool>* each) {
+  // each: one verdict per cell (kzgx_verify_cells_each*) instead of the aggregate's one answer
   const size_t m = proofs.size(), nc = commits.size();
   const unsigned kl = coset_cells_log2l(m, nc, commit_index, cell_index, values, log2n, extended);
+  if (each) each->clear();
   if (m == 0) return true;
   const size_t l = values[0].size();
   const int nl = base_limbs();
@@ -1053,6 +1080,24 @@ bool trusted_setup::coset_aggregated(std::vector<commit>& commits, const std::ve
     for (size_t j = 0; j < l; j++) std::memcpy(&y[4 * (k * l + j)], values[k][j].v.data(), 32);
   }
   const int flags = (extended ? KZGX_PROVE_COSETS_EXTENDED : 0) | (bit_reversed ? KZGX_NTT_BITREV : 0);
+  if (each) {
+    std::vector<int> oks(m, 0);
+    if (checked)
+      check(kzgx_verify_cells_each_checked(ctx, c.data(), ci.data(), nc, commit_index.data(), cell_index.data(),
+                                           p.data(), pi.data(), y.data(), m, log2n, kl, flags, check_subgroup ? 1 : 0,
+                                           oks.data()),
+            "kzgx_verify_cells_each_checked");
+    else
+      check(kzgx_verify_cells_each(ctx, c.data(), ci.data(), nc, commit_index.data(), cell_index.data(), p.data(),
+                                   pi.data(), y.data(), m, log2n, kl, flags, oks.data()),
+            "kzgx_verify_cells_each");
+    bool all = true;
+    for (int v : oks) {
+      each->push_back(v != 0);
+      all = all && v != 0;
+    }
+    return all;
+  }
   int ok = 0;
   if (checked)
     check(kzgx_verify_cells_aggregate_checked(ctx, c.data(), ci.data(), nc, commit_index.data(), cell_index.data(),

@@ -42,6 +42,14 @@ struct kzgx_ctx {
   size_t vw_b = 0;
   bool vw_ready = false;
   size_t vw_max = 8192;  // batches up to this size take the wave path
+  // per-cell verification (kzgx_verify_cells_each), per coset size l: the staged
+  // pair G2[0] || G2[l] of the lane path and, on the wave path's first use, the
+  // buffer verify_wave_prepare builds from it; dropped when either SRS changes
+  struct CellsG2 {
+    uint32_t *d_q = nullptr, *d_vw = nullptr;
+  };
+  std::map<size_t, CellsG2> cells_g2;
+  size_t cells_chunk = 0;  // cells per internal chunk (0 = KZGX_VERIFY_CELLS_EACH_CHUNK)
   // windowed multiples of the G2 SRS for polyeval_G2 (built on first use)
   uint32_t* d_g2tab = nullptr;
   size_t g2tab_b = 0;
@@ -65,6 +73,16 @@ struct kzgx_ctx {
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
+
+// a setup changed: the per-cell verify's G2 pairs and line tables are stale
+// (hipFree waits for the work that may still read them)
+static void cells_g2_drop(kzgx_ctx* ctx) {
+  for (auto& e : ctx->cells_g2) {
+    if (e.second.d_q) (void)hipFree(e.second.d_q);
+    if (e.second.d_vw) (void)hipFree(e.second.d_vw);
+  }
+  ctx->cells_g2.clear();
+}
 
 namespace kzgx {
 
@@ -588,6 +606,7 @@ void kzgx_destroy(kzgx_ctx* ctx) {
   (void)hipSetDevice(ctx->c.device);
   (void)hipStreamSynchronize(ctx->c.stream);
   (void)kzgx_prof_clear(ctx);
+  cells_g2_drop(ctx);
   Ctx& c = ctx->c;
   void* bufs[] = {c.d_table, c.d_table_small, c.d_table_big, c.d_inf, c.d_stage[0], c.d_stage[1], c.d_stage[2], c.d_stage[3],
                   c.d_poly_ws, c.d_poly_ws2, ctx->d_srs_canon, ctx->d_srs2_canon, c.d_g2_ws, ctx->d_vw, ctx->d_g2tab,
@@ -878,6 +897,7 @@ size_t kzgx_srs_size(const kzgx_ctx* ctx) { return ctx ? ctx->c.n_srs : 0; }
 int kzgx_load_srs_g1(kzgx_ctx* ctx, const uint64_t* xy, size_t n) {
   KZGX_TRY(activate(ctx));
   ctx->vw_ready = false;
+  cells_g2_drop(ctx);
   kzgx::prove_all_drop(&ctx->c);
   if (!xy || n == 0) return KZGX_ERR_ARG;
   const size_t bytes = n * point_words(ctx) * 4;
@@ -891,6 +911,7 @@ int kzgx_load_srs_g1(kzgx_ctx* ctx, const uint64_t* xy, size_t n) {
 int kzgx_gen_srs_g1(kzgx_ctx* ctx, const uint64_t* tau, size_t start, size_t n) {
   KZGX_TRY(activate(ctx));
   ctx->vw_ready = false;
+  cells_g2_drop(ctx);
   kzgx::prove_all_drop(&ctx->c);
   if (!tau || n == 0 || n > 0x7fffffffu) return KZGX_ERR_ARG;
   const size_t bytes = n * point_words(ctx) * 4;
@@ -1370,6 +1391,7 @@ size_t kzgx_srs_g2_size(const kzgx_ctx* ctx) { return ctx ? ctx->n_srs2 : 0; }
 int kzgx_gen_srs_g2(kzgx_ctx* ctx, const uint64_t* tau, size_t start, size_t n) {
   KZGX_TRY(activate(ctx));
   ctx->vw_ready = false;
+  cells_g2_drop(ctx);
   ctx->g2tab_n = 0;
   if (!tau || n == 0 || n > 0x7fffffffu) return KZGX_ERR_ARG;
   const size_t bytes = n * 2 * point_words(ctx) * 4;
@@ -1400,6 +1422,7 @@ int kzgx_gen_srs_g2(kzgx_ctx* ctx, const uint64_t* tau, size_t start, size_t n) 
 int kzgx_load_srs_g2(kzgx_ctx* ctx, const uint64_t* xy, size_t n) {
   KZGX_TRY(activate(ctx));
   ctx->vw_ready = false;
+  cells_g2_drop(ctx);
   ctx->g2tab_n = 0;
   if (!xy || n == 0) return KZGX_ERR_ARG;
   const size_t bytes = n * 2 * point_words(ctx) * 4;
@@ -2548,6 +2571,208 @@ int kzgx_verify_cells_aggregate_checked(kzgx_ctx* ctx, const uint64_t* commits_x
                                         int flags, int subgroup, int* ok) {
   return verify_cells_host(ctx, commits_xy, commit_inf, n_commits, commit_index, cell_index, proofs_xy, proof_inf, ys,
                            challenges, count, log2n, log2l, flags, true, subgroup, ok);
+}
+
+}  // extern "C"
+
+// ---- per-cell verdicts -------------------------------------------------------------------------
+namespace {
+// cells per chunk: the setter's value or the default, and at most
+// KZGX_VERIFY_CELLS_EACH_CHUNK_VALUES scalars of transforms
+size_t cells_each_chunk(const kzgx_ctx* ctx, unsigned log2l) {
+  const size_t want = ctx->cells_chunk ? ctx->cells_chunk : (size_t)KZGX_VERIFY_CELLS_EACH_CHUNK;
+  return std::max<size_t>(1, std::min(want, (size_t)KZGX_VERIFY_CELLS_EACH_CHUNK_VALUES >> log2l));
+}
+
+// the staged G2[0] || G2[l] and, for the wave path, its line tables
+int cells_g2_ensure(kzgx_ctx* ctx, size_t l, bool wave, hipStream_t st, const kzgx_ctx::CellsG2** out) {
+  kzgx_ctx::CellsG2& e = ctx->cells_g2[l];
+  const size_t p2 = 2 * point_words(ctx) * 4;
+  if (!e.d_q) {
+    uint32_t* q = nullptr;
+    KZGX_TRY_HIP(hipMalloc((void**)&q, 2 * p2));
+    hipError_t r = hipMemcpyAsync(q, ctx->d_srs2_canon, p2, hipMemcpyDeviceToDevice, st);
+    if (r == hipSuccess)
+      r = hipMemcpyAsync((char*)q + p2, (const char*)ctx->d_srs2_canon + l * p2, p2, hipMemcpyDeviceToDevice, st);
+    if (r == hipSuccess) r = hipStreamSynchronize(st);  // one-time; later calls may come on other streams
+    if (r != hipSuccess) {
+      (void)hipFree(q);
+      return kzgx::hip_fail(r);
+    }
+    e.d_q = q;
+  }
+  if (wave && !e.d_vw) {
+    uint32_t* b = nullptr;
+    KZGX_TRY_HIP(hipMalloc((void**)&b, kzgx::verify_wave_bytes(ctx->c.curve)));
+    kzgx::GenTables g;
+    int r = kzgx::gen_tables_get(ctx->c.curve, ctx->c.device, st, &g);
+    if (r == KZGX_OK) r = kzgx::verify_wave_prepare(&ctx->c, ctx->d_srs_canon, e.d_q, g.g1_comb, b, st);
+    if (r == KZGX_OK && hipStreamSynchronize(st) != hipSuccess) r = KZGX_ERR_HIP;
+    if (r != KZGX_OK) {
+      (void)hipFree(b);
+      return r;
+    }
+    e.d_vw = b;
+  }
+  *out = &e;
+  return KZGX_OK;
+}
+
+// ok[k] = e(pi_k, G2[l]) == e(C_(c_k) - [I_k(tau)]G1 + [a_(i_k)]pi_k, G2[0]), in chunks of cells:
+// inverse transforms, the interpolants' coefficients, one batched MSM over the SRS prefix,
+// C' = C - [I(tau)]G1, then kzgx_verify_single_batch_device's two kernels on (C', pi, z = a, y = 0)
+// against G2[0], G2[l]
+int cells_each_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, size_t n_commits,
+                      const void* d_commit_index, const void* d_cell_index, const void* d_proofs,
+                      const void* d_proof_inf, const void* d_ys, size_t count, unsigned log2n, unsigned log2l,
+                      int flags, bool checked, int subgroup, void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (count > 0 &&
+      (!d_ok || !d_commit_index || !d_cell_index || !d_proofs || !d_ys || (n_commits > 0 && !d_commits)))
+    return KZGX_ERR_ARG;
+  CellsShape sh;
+  KZGX_TRY(cells_args(ctx, n_commits, count, log2n, log2l, flags, &sh));
+  if (count == 0) return KZGX_OK;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::Ctx* c = &ctx->c;
+  const bool wave = count <= ctx->vw_max;
+  const kzgx_ctx::CellsG2* g2;
+  KZGX_TRY(cells_g2_ensure(ctx, sh.l, wave, st, &g2));
+  kzgx::WsLease ws = c->ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const size_t pw = point_words(ctx), l = sh.l, chunk = cells_each_chunk(ctx, log2l), cc = std::min(chunk, count);
+  // the chunk's interpolants; a | y = 0; [I(tau)]G1 | C' | their flags | bad
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->ntt_coef, cc * l * 32, &ws->ntt_coef_b));
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->var_scal, 2 * cc * 32, &ws->var_scal_b));
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->var_pt, (2 * cc * pw + 3 * cc) * 4, &ws->var_pt_b));
+  uint32_t* a = ws->var_scal;
+  uint32_t* zero = a + cc * 8;
+  uint32_t* I = ws->var_pt;
+  uint32_t* D = I + cc * pw;
+  uint32_t* I_inf = D + cc * pw;
+  uint32_t* D_inf = I_inf + cc;
+  uint32_t* bad = D_inf + cc;
+  uint32_t* f = nullptr;  // commit flags | the chunk's proof flags
+  if (checked) KZGX_TRY(chk_scratch(ctx, ws, n_commits + cc, &f));
+  KZGX_TRY(kzgx::ntt_twiddles(c, sh.kD, st));
+  KZGX_TRY_HIP(hipMemsetAsync(zero, 0, cc * 32, st));
+  const uint32_t* cidx = (const uint32_t*)d_commit_index;
+  const uint32_t* kidx = (const uint32_t*)d_cell_index;
+  const uint32_t* pr = (const uint32_t*)d_proofs;
+  const uint32_t* pf = (const uint32_t*)d_proof_inf;
+  uint32_t* ok = (uint32_t*)d_ok;
+  for (size_t k0 = 0; k0 < count; k0 += chunk) {
+    const size_t m = std::min(chunk, count - k0);
+    const uint32_t* pfk = pf ? pf + k0 : nullptr;
+    if (checked)  // the commitments ride with the first chunk's proofs
+      KZGX_TRY(kzgx::g1_check2(c, (const uint32_t*)d_commits, (const uint32_t*)d_commit_inf, k0 ? 0 : n_commits,
+                               pr + k0 * pw, pfk, m, subgroup, k0 ? f + n_commits : f, st));
+    {
+      kzgx::ProfScope p(c, st, "cells_intt");
+      KZGX_TRY(kzgx::ntt(c, (const uint32_t*)d_ys + k0 * l * 8, l, ws->ntt_coef, l, log2l, m, true, sh.bitrev, st));
+    }
+    KZGX_TRY(kzgx::cells_coeffs(c, ws->ntt_coef, kidx + k0, cidx + k0, m, n_commits, log2l, sh.kD, sh.bitrev, a, bad,
+                                st));
+    {
+      kzgx::ProfScope p(c, st, "cells_msm");
+      KZGX_TRY(kzgx::msm_batch(c, ws->ntt_coef, l, m, l * 8, I, I_inf, st));
+    }
+    KZGX_TRY(kzgx::cells_sub(c, (const uint32_t*)d_commits, (const uint32_t*)d_commit_inf, cidx + k0, bad, I, I_inf,
+                             m, D, D_inf, st));
+    if (wave)
+      KZGX_TRY(kzgx::verify_wave_batch(c, D, D_inf, pr + k0 * pw, pfk, a, zero, m, ctx->d_srs_canon, g2->d_vw,
+                                       ok + k0, st));
+    else
+      KZGX_TRY(kzgx::verify_single_batch(c, D, D_inf, pr + k0 * pw, pfk, a, zero, m, ctx->d_srs_canon, g2->d_q,
+                                         ok + k0, st));
+    KZGX_TRY(kzgx::cells_gate(ok + k0, bad, cidx + k0, f, f ? f + n_commits : nullptr, m, st));
+  }
+  return KZGX_OK;
+}
+
+// the host-pointer forms: staging and the index checks of verify_cells_host, count verdicts back
+int cells_each_host(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                    const uint32_t* commit_index, const uint32_t* cell_index, const uint64_t* proofs_xy,
+                    const int* proof_inf, const uint64_t* ys, size_t count, unsigned log2n, unsigned log2l, int flags,
+                    bool checked, int subgroup, int* ok) {
+  KZGX_TRY(activate(ctx));
+  if (count > 0 && (!ok || !commit_index || !cell_index || !proofs_xy || !ys || (n_commits > 0 && !commits_xy)))
+    return KZGX_ERR_ARG;
+  CellsShape sh;
+  KZGX_TRY(cells_args(ctx, n_commits, count, log2n, log2l, flags, &sh));
+  if (count == 0) return KZGX_OK;
+  for (size_t k = 0; k < count; k++)
+    if (commit_index[k] >= n_commits || (cell_index[k] >> sh.kR)) return KZGX_ERR_ARG;
+  const size_t pb = point_words(ctx) * 4, yb = count * sh.l * 32, np = n_commits + count;
+  void *d_c, *d_p, *d_s, *d_f;
+  KZGX_TRY(stage(ctx, 0, n_commits * pb + 16, &d_c));
+  KZGX_TRY(stage(ctx, 1, count * pb, &d_p));
+  KZGX_TRY(stage(ctx, 2, yb, &d_s));
+  KZGX_TRY(stage(ctx, 3, (np + 3 * count) * 4, &d_f));
+  // commit flags | proof flags | commit_index | cell_index | ok
+  std::vector<uint32_t> fl(np + 2 * count);
+  for (size_t k = 0; k < n_commits; k++) fl[k] = commit_inf ? (uint32_t)(commit_inf[k] != 0) : 0u;
+  for (size_t k = 0; k < count; k++) {
+    fl[n_commits + k] = proof_inf ? (uint32_t)(proof_inf[k] != 0) : 0u;
+    fl[np + k] = commit_index[k];
+    fl[np + count + k] = cell_index[k];
+  }
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_c, commits_xy, n_commits * pb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_p, proofs_xy, count * pb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_s, ys, yb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_f, fl.data(), fl.size() * 4, hipMemcpyHostToDevice, st));
+  uint32_t* f = (uint32_t*)d_f;
+  uint32_t* d_ok = f + np + 2 * count;
+  KZGX_TRY(cells_each_device(ctx, d_c, f, n_commits, f + np, f + np + count, d_p, f + n_commits, d_s, count, log2n,
+                             log2l, flags, checked, subgroup, d_ok, nullptr));
+  std::vector<uint32_t> v(count);
+  KZGX_TRY_HIP(hipMemcpyAsync(v.data(), d_ok, count * 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t k = 0; k < count; k++) ok[k] = v[k] ? 1 : 0;
+  return KZGX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kzgx_verify_cells_each_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, size_t n_commits,
+                                  const void* d_commit_index, const void* d_cell_index, const void* d_proofs,
+                                  const void* d_proof_inf, const void* d_ys, size_t count, unsigned log2n,
+                                  unsigned log2l, int flags, void* d_ok, void* stream) {
+  return cells_each_device(ctx, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index, d_proofs,
+                           d_proof_inf, d_ys, count, log2n, log2l, flags, false, 0, d_ok, stream);
+}
+
+int kzgx_verify_cells_each_checked_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                          size_t n_commits, const void* d_commit_index, const void* d_cell_index,
+                                          const void* d_proofs, const void* d_proof_inf, const void* d_ys,
+                                          size_t count, unsigned log2n, unsigned log2l, int flags, int subgroup,
+                                          void* d_ok, void* stream) {
+  return cells_each_device(ctx, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index, d_proofs,
+                           d_proof_inf, d_ys, count, log2n, log2l, flags, true, subgroup, d_ok, stream);
+}
+
+int kzgx_verify_cells_each(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                           const uint32_t* commit_index, const uint32_t* cell_index, const uint64_t* proofs_xy,
+                           const int* proof_inf, const uint64_t* ys, size_t count, unsigned log2n, unsigned log2l,
+                           int flags, int* ok) {
+  return cells_each_host(ctx, commits_xy, commit_inf, n_commits, commit_index, cell_index, proofs_xy, proof_inf, ys,
+                         count, log2n, log2l, flags, false, 0, ok);
+}
+
+int kzgx_verify_cells_each_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf,
+                                   size_t n_commits, const uint32_t* commit_index, const uint32_t* cell_index,
+                                   const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* ys, size_t count,
+                                   unsigned log2n, unsigned log2l, int flags, int subgroup, int* ok) {
+  return cells_each_host(ctx, commits_xy, commit_inf, n_commits, commit_index, cell_index, proofs_xy, proof_inf, ys,
+                         count, log2n, log2l, flags, true, subgroup, ok);
+}
+
+int kzgx_set_verify_cells_chunk(kzgx_ctx* ctx, size_t cells) {
+  if (!ctx || cells > 65535) return KZGX_ERR_ARG;
+  ctx->cells_chunk = cells;
+  return KZGX_OK;
 }
 
 }  // extern "C"

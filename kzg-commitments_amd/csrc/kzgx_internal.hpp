@@ -419,6 +419,20 @@ size_t cells_fold_slices(size_t count, unsigned log2l);
 int cells_scalars(Ctx* ctx, const uint32_t* d_T, const uint32_t* d_r, const uint32_t* d_cell_index,
                   const uint32_t* d_commit_index, size_t count, size_t n_commits, unsigned log2l, unsigned log2D,
                   bool bitrev, uint32_t* d_out, uint32_t* d_gate, hipStream_t st);
+// verify_cells_each (poly.hip, pairing.hip).  cells_coeffs: in place, d_T = the count x l inverse transforms
+// becomes the cells' interpolants I_k (canonical coefficients); d_a[k] = a_(i_k) (canonical), d_bad[k] = 1
+// iff commit_index[k] >= n_commits or cell_index[k] >= R.  The twiddle table as for cells_scalars.
+// cells_sub: d_out[k] = commits[commit_index[k]] - d_b[k] (canonical affine, infinity flags; no gather for a
+// bad cell).  cells_gate: d_ok[k] &= !d_bad[k], and, with d_commit_ok / d_proof_ok (both or neither), &=
+// d_commit_ok[commit_index[k]] & d_proof_ok[k].
+int cells_coeffs(Ctx* ctx, uint32_t* d_T, const uint32_t* d_cell_index, const uint32_t* d_commit_index, size_t count,
+                 size_t n_commits, unsigned log2l, unsigned log2D, bool bitrev, uint32_t* d_a, uint32_t* d_bad,
+                 hipStream_t st);
+int cells_sub(Ctx* ctx, const uint32_t* d_commits, const uint32_t* d_commit_inf, const uint32_t* d_commit_index,
+              const uint32_t* d_bad, const uint32_t* d_b, const uint32_t* d_b_inf, size_t count, uint32_t* d_out,
+              uint32_t* d_out_inf, hipStream_t st);
+int cells_gate(uint32_t* d_ok, const uint32_t* d_bad, const uint32_t* d_commit_index, const uint32_t* d_commit_ok,
+               const uint32_t* d_proof_ok, size_t count, hipStream_t st);
 // one MSM as an XYZZ record, no affine conversion (msm.hip)
 int msm_partial_xyzz(Ctx* ctx, const uint32_t* d_scalars, size_t n, uint32_t* d_rec, hipStream_t st);
 int gen_srs_points(Ctx* ctx, const uint32_t* tau_canon_host, size_t start, size_t n, uint32_t* d_out_canon,

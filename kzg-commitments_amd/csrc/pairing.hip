@@ -415,6 +415,37 @@ __global__ __launch_bounds__(64) void k_g1_sub(const uint32_t* __restrict__ a, c
   *out_inf = fin ? 0u : 1u;
 }
 
+// per-cell verification (kzgx_verify_cells_each): lane k writes
+// out[k] = commits[commit_index[k]] - b[k], canonical affine with an infinity
+// flag.  The commitment is gathered only when bad[k] == 0 (its index is then
+// in range); a bad cell gets -b[k], and its verdict is forced to 0 afterwards.
+// The additions are complete: equal operands give infinity, opposite ones the
+// doubling.
+template <class C>
+__global__ __launch_bounds__(64) void k_cells_sub(const uint32_t* __restrict__ commits,
+                                                  const uint32_t* __restrict__ commit_inf,
+                                                  const uint32_t* __restrict__ commit_index,
+                                                  const uint32_t* __restrict__ bad, const uint32_t* __restrict__ b,
+                                                  const uint32_t* __restrict__ b_inf, uint32_t count,
+                                                  uint32_t* __restrict__ out, uint32_t* __restrict__ out_inf) {
+  constexpr int N = C::Fp::N;
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  Xyzz<C> acc = xyzz_inf<C>();
+  Affine<C> pa, pb;
+  if (!bad[k]) {
+    const uint32_t c = commit_index[k];
+    if (affine_from_canonical<C>(commits + (size_t)c * 2 * N, pa) && !(commit_inf && commit_inf[c]))
+      acc = xyzz_from_affine<C>(pa);
+  }
+  if (affine_from_canonical<C>(b + (size_t)k * 2 * N, pb) && !b_inf[k])
+    acc = xyzz_add_affine<C>(acc, affine_neg<C>(pb));
+  Affine<C> d;
+  const bool fin = xyzz_to_affine<C>(acc, d);
+  affine_to_canonical<C>(out + (size_t)k * 2 * N, d, fin);
+  out_inf[k] = fin ? 0u : 1u;
+}
+
 // ---- batched single-point verify -----------------------------------------------
 // thread per opening: verify_proof with one point (x = z, y), i.e.
 //   e(pi, [tau - z]G2) == e(C - [y]G1, G2)
@@ -598,6 +629,22 @@ int verify_single_batch(Ctx* ctx, const uint32_t* d_commits, const uint32_t* d_c
   else
     hipLaunchKernelGGL(k_verify_single<BLS12381G1>, grd, blk, 0, st, d_commits, d_commit_inf, d_proofs, d_proof_inf,
                        d_z, d_y, (uint32_t)count, d_g1_0, d_g2_01, d_ok);
+  KZGX_TRY_HIP(hipGetLastError());
+  return KZGX_OK;
+}
+
+int cells_sub(Ctx* ctx, const uint32_t* d_commits, const uint32_t* d_commit_inf, const uint32_t* d_commit_index,
+              const uint32_t* d_bad, const uint32_t* d_b, const uint32_t* d_b_inf, size_t count, uint32_t* d_out,
+              uint32_t* d_out_inf, hipStream_t st) {
+  if (count == 0) return KZGX_OK;
+  dim3 blk(64), grd((unsigned)((count + 63) / 64));
+  ProfScope p(ctx, st, "cells_sub");
+  if (ctx->curve == KZGX_CURVE_BN254)
+    hipLaunchKernelGGL(k_cells_sub<BN254G1>, grd, blk, 0, st, d_commits, d_commit_inf, d_commit_index, d_bad, d_b,
+                       d_b_inf, (uint32_t)count, d_out, d_out_inf);
+  else
+    hipLaunchKernelGGL(k_cells_sub<BLS12381G1>, grd, blk, 0, st, d_commits, d_commit_inf, d_commit_index, d_bad, d_b,
+                       d_b_inf, (uint32_t)count, d_out, d_out_inf);
   KZGX_TRY_HIP(hipGetLastError());
   return KZGX_OK;
 }

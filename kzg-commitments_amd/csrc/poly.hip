@@ -1016,6 +1016,83 @@ int cells_scalars(Ctx* ctx, const uint32_t* d_T, const uint32_t* d_r, const uint
                                               log2D, bitrev, d_out, d_gate, st);
 }
 
+// --------------------------------------------------------------------------
+// per-cell verification: every cell's own interpolant (kzgx_verify_cells_each)
+// --------------------------------------------------------------------------
+// k_cells_coeffs: one thread per (cell, t), threads along t as in k_cells_fold.
+// In place, T[k][t] = INTT_l(y_k)[t] becomes I_k's coefficient w^(-i_k t) T[k][t]
+// (canonical); the thread of t = 0 also writes a_(i_k) = w^(i_k l) (canonical) and
+// bad[k] = "cell k names a coset >= R or a commitment >= nc".  The same index
+// rules as k_cells_fold: the coset is reduced mod R before it picks a twiddle,
+// the commitment index is only compared.
+template <class FR>
+__global__ __launch_bounds__(256) void k_cells_coeffs(uint32_t* __restrict__ T,
+                                                      const uint32_t* __restrict__ cell_index,
+                                                      const uint32_t* __restrict__ commit_index, uint32_t count,
+                                                      uint32_t n_commits, uint32_t kl, uint32_t kD, uint32_t bitrev,
+                                                      const uint32_t* __restrict__ table, uint32_t K,
+                                                      uint32_t* __restrict__ a_out, uint32_t* __restrict__ bad) {
+  constexpr int N = FR::N;
+  const uint32_t kR = kD - kl, R = 1u << kR, D = 1u << kD;
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint32_t k = (uint32_t)(g >> kl), t = (uint32_t)g & ((1u << kl) - 1);
+  if (k >= count) return;
+  const uint32_t p = cell_index[k];
+  const uint32_t i = bitrev ? (kR ? __brev(p) >> (32 - kR) : 0u) : p & (R - 1);
+  if (t) {  // t = 0: the twiddle is 1
+    uint32_t* v = T + (((size_t)k << kl) + t) * N;
+    fe_store<FR>(v, fe_mul<FR>(fe_load<FR>(v), ntt_tw<FR>(table, K, kD, (uint32_t)(((uint64_t)i * t) & (D - 1)), true)));
+    return;
+  }
+  bad[k] = ((p >= R) | (commit_index[k] >= n_commits)) ? 1u : 0u;
+  Fe<FR> a = fe_zero<FR>();
+  a.v[0] = 1;
+  if (kD) a = fe_from_mont<FR>(ntt_tw<FR>(table, K, kD, (uint32_t)(((uint64_t)i << kl) & (D - 1)), false));
+  fe_store<FR>(a_out + (size_t)k * N, a);
+}
+
+// ok[k] = ok[k] && !bad[k], and with the point checks' flags (commit_ok by
+// commitment, proof_ok by cell) && commit_ok[c_k] && proof_ok[k]; a bad cell's
+// commitment index is not used
+__global__ __launch_bounds__(256) void k_cells_gate(uint32_t* __restrict__ ok, const uint32_t* __restrict__ bad,
+                                                    const uint32_t* __restrict__ commit_index,
+                                                    const uint32_t* __restrict__ commit_ok,
+                                                    const uint32_t* __restrict__ proof_ok, uint32_t count) {
+  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= count) return;
+  bool v = ok[k] != 0u && bad[k] == 0u;
+  if (v && commit_ok) v = commit_ok[commit_index[k]] != 0u && proof_ok[k] != 0u;
+  ok[k] = v ? 1u : 0u;
+}
+
+int cells_coeffs(Ctx* ctx, uint32_t* d_T, const uint32_t* d_cell_index, const uint32_t* d_commit_index, size_t count,
+                 size_t n_commits, unsigned log2l, unsigned log2D, bool bitrev, uint32_t* d_a, uint32_t* d_bad,
+                 hipStream_t st) {
+  if (count == 0 || log2l > log2D || (log2D > 0 && (int)log2D > ctx->ntt_log2) || (count << log2l) > 0xffffffffu)
+    return KZGX_ERR_ARG;
+  ProfScope p(ctx, st, "cells_coeffs");
+  const dim3 grd((unsigned)(((count << log2l) + 255) / 256)), blk(256);
+  if (ctx->curve == KZGX_CURVE_BN254)
+    hipLaunchKernelGGL(k_cells_coeffs<BN254Fr>, grd, blk, 0, st, d_T, d_cell_index, d_commit_index, (uint32_t)count,
+                       (uint32_t)n_commits, log2l, log2D, bitrev ? 1u : 0u, ctx->d_ntt_tw, (uint32_t)ctx->ntt_log2,
+                       d_a, d_bad);
+  else
+    hipLaunchKernelGGL(k_cells_coeffs<BLS12381Fr>, grd, blk, 0, st, d_T, d_cell_index, d_commit_index,
+                       (uint32_t)count, (uint32_t)n_commits, log2l, log2D, bitrev ? 1u : 0u, ctx->d_ntt_tw,
+                       (uint32_t)ctx->ntt_log2, d_a, d_bad);
+  KZGX_TRY_HIP(hipGetLastError());
+  return KZGX_OK;
+}
+
+int cells_gate(uint32_t* d_ok, const uint32_t* d_bad, const uint32_t* d_commit_index, const uint32_t* d_commit_ok,
+               const uint32_t* d_proof_ok, size_t count, hipStream_t st) {
+  if (count == 0) return KZGX_OK;
+  hipLaunchKernelGGL(k_cells_gate, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, d_ok, d_bad,
+                     d_commit_index, d_commit_ok, d_proof_ok, (uint32_t)count);
+  KZGX_TRY_HIP(hipGetLastError());
+  return KZGX_OK;
+}
+
 }  // namespace kzgx
 
 namespace kzgx {

@@ -44,6 +44,8 @@ EXPORTS = [
     "kzgx_coset_points", "kzgx_prove_cosets_prepare", "kzgx_prove_cosets_batch", "kzgx_prove_cosets_batch_device",
     "kzgx_verify_cells_aggregate", "kzgx_verify_cells_aggregate_device", "kzgx_verify_cells_aggregate_checked",
     "kzgx_verify_cells_aggregate_checked_device",
+    "kzgx_verify_cells_each", "kzgx_verify_cells_each_device", "kzgx_verify_cells_each_checked",
+    "kzgx_verify_cells_each_checked_device", "kzgx_set_verify_cells_chunk",
     "kzgx_recover_cells", "kzgx_recover_cells_device", "kzgx_recover_cells_and_proofs",
     "kzgx_recover_cells_and_proofs_device",
     "kzgx_point_bytes", "kzgx_g1_decompress_batch", "kzgx_g1_decompress_batch_device", "kzgx_g1_compress_batch",
@@ -222,6 +224,17 @@ def lib():
             "kzgx_verify_cells_aggregate_checked_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz,
                                                                           ctypes.c_uint, ctypes.c_uint, ctypes.c_int,
                                                                           ctypes.c_int, vp, vp]),
+            "kzgx_verify_cells_each": (ctypes.c_int, [vp, u64p, intp, sz, u32p, u32p, u64p, intp, u64p, sz,
+                                                      ctypes.c_uint, ctypes.c_uint, ctypes.c_int, intp]),
+            "kzgx_verify_cells_each_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, ctypes.c_uint,
+                                                             ctypes.c_uint, ctypes.c_int, vp, vp]),
+            "kzgx_verify_cells_each_checked": (ctypes.c_int, [vp, u64p, intp, sz, u32p, u32p, u64p, intp, u64p, sz,
+                                                              ctypes.c_uint, ctypes.c_uint, ctypes.c_int,
+                                                              ctypes.c_int, intp]),
+            "kzgx_verify_cells_each_checked_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, vp, vp, vp, sz,
+                                                                     ctypes.c_uint, ctypes.c_uint, ctypes.c_int,
+                                                                     ctypes.c_int, vp, vp]),
+            "kzgx_set_verify_cells_chunk": (ctypes.c_int, [vp, sz]),
             "kzgx_recover_cells": (ctypes.c_int, [vp, u32p, u32p, u64p, sz, sz, ctypes.c_uint, ctypes.c_uint,
                                                   ctypes.c_int, u64p, u64p, intp]),
             "kzgx_recover_cells_device": (ctypes.c_int, [vp, vp, vp, vp, sz, sz, ctypes.c_uint, ctypes.c_uint,
@@ -977,8 +990,8 @@ class Context:
              "kzgx_prove_cosets_batch_device")
 
     # ---- aggregated cell verification ----
-    def _cells_host(self, fn, name, commits, commit_index, cell_index, proofs, ys, log2n, challenges, commit_inf,
-                    proof_inf, extended, bitrev, extra):
+    def _cells_marshal(self, commits, commit_index, cell_index, proofs, ys, commit_inf, proof_inf):
+        """the cell entries' arrays: (leading ABI arguments up to ys, count, log2l, the arrays kept alive)"""
         c = np.ascontiguousarray(commits, dtype=np.uint64).reshape(-1, 2 * self.w64)
         p = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 2 * self.w64)
         y = np.ascontiguousarray(ys, dtype=np.uint64)
@@ -988,18 +1001,34 @@ class Context:
         nc, n = c.shape[0], p.shape[0]
         ci = np.ascontiguousarray(commit_index, dtype=np.uint32).reshape(-1)
         ki = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)
-        r = None if challenges is None or not n else as_scalars(challenges)
-        assert y.shape[0] == n and ci.shape[0] == n and ki.shape[0] == n and (r is None or r.shape[0] == n)
+        assert y.shape[0] == n and ci.shape[0] == n and ki.shape[0] == n
         fc = None if commit_inf is None else np.ascontiguousarray(commit_inf, dtype=np.int32)
         fp = None if proof_inf is None else np.ascontiguousarray(proof_inf, dtype=np.int32)
         assert (fc is None or fc.shape[0] == nc) and (fp is None or fp.shape[0] == n)
-        ok = ctypes.c_int(0)
-        _chk(fn(self.h, _p(c) if nc else None, None if fc is None else fc.ctypes.data_as(intp), nc,
+        head = (self.h, _p(c) if nc else None, None if fc is None else fc.ctypes.data_as(intp), nc,
                 ci.ctypes.data_as(u32p) if n else None, ki.ctypes.data_as(u32p) if n else None,
-                _p(p) if n else None, None if fp is None else fp.ctypes.data_as(intp), _p(y) if n else None,
-                None if r is None else _p(r), n, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), *extra,
+                _p(p) if n else None, None if fp is None else fp.ctypes.data_as(intp), _p(y) if n else None)
+        return head, n, log2l, (c, p, y, ci, ki, fc, fp)
+
+    def _cells_host(self, fn, name, commits, commit_index, cell_index, proofs, ys, log2n, challenges, commit_inf,
+                    proof_inf, extended, bitrev, extra):
+        head, n, log2l, _keep = self._cells_marshal(commits, commit_index, cell_index, proofs, ys, commit_inf,
+                                                    proof_inf)
+        r = None if challenges is None or not n else as_scalars(challenges)
+        assert r is None or r.shape[0] == n
+        ok = ctypes.c_int(0)
+        _chk(fn(*head, None if r is None else _p(r), n, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), *extra,
                 ctypes.byref(ok)), name)
         return bool(ok.value)
+
+    def _cells_each_host(self, fn, name, commits, commit_index, cell_index, proofs, ys, log2n, commit_inf, proof_inf,
+                         extended, bitrev, extra):
+        head, n, log2l, _keep = self._cells_marshal(commits, commit_index, cell_index, proofs, ys, commit_inf,
+                                                    proof_inf)
+        ok = np.zeros(n, dtype=np.int32)
+        _chk(fn(*head, n, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), *extra,
+                ok.ctypes.data_as(intp) if n else None), name)
+        return ok.astype(bool)
 
     def verify_cells_aggregate(self, commits, commit_index, cell_index, proofs, ys, log2n, challenges=None,
                                commit_inf=None, proof_inf=None, extended=False, bitrev=False) -> bool:
@@ -1037,6 +1066,43 @@ class Context:
             self.h, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index, d_proofs, d_proof_inf, d_ys,
             d_challenges, count, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), int(bool(subgroup)), d_ok,
             stream), "kzgx_verify_cells_aggregate_checked_device")
+
+    def verify_cells_each(self, commits, commit_index, cell_index, proofs, ys, log2n, commit_inf=None,
+                          proof_inf=None, extended=False, bitrev=False) -> np.ndarray:
+        """kzgx_verify_cells_each: verify_cells_aggregate's batch, one boolean per cell (count,) -- the answer
+        verify_proof gives for that cell over coset_points(...); no challenges, exact per cell."""
+        return self._cells_each_host(lib().kzgx_verify_cells_each, "kzgx_verify_cells_each", commits, commit_index,
+                                     cell_index, proofs, ys, log2n, commit_inf, proof_inf, extended, bitrev, ())
+
+    def verify_cells_each_checked(self, commits, commit_index, cell_index, proofs, ys, log2n, commit_inf=None,
+                                  proof_inf=None, extended=False, bitrev=False, subgroup: bool = False) -> np.ndarray:
+        """verify_cells_each behind the G1 check: False for a cell whose proof or commitment fails it."""
+        return self._cells_each_host(lib().kzgx_verify_cells_each_checked, "kzgx_verify_cells_each_checked", commits,
+                                     commit_index, cell_index, proofs, ys, log2n, commit_inf, proof_inf, extended,
+                                     bitrev, (int(bool(subgroup)),))
+
+    def verify_cells_each_device(self, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index, d_proofs,
+                                 d_proof_inf, d_ys, count, log2n, log2l, d_ok, extended=False, bitrev=False,
+                                 stream=None):
+        """kzgx_verify_cells_each_device: device pointers (uint32 indices and flags), d_ok count uint32,
+        enqueued on stream."""
+        _chk(lib().kzgx_verify_cells_each_device(
+            self.h, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index, d_proofs, d_proof_inf, d_ys,
+            count, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), d_ok, stream),
+            "kzgx_verify_cells_each_device")
+
+    def verify_cells_each_checked_device(self, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index,
+                                         d_proofs, d_proof_inf, d_ys, count, log2n, log2l, subgroup, d_ok,
+                                         extended=False, bitrev=False, stream=None):
+        """kzgx_verify_cells_each_checked_device: the same behind the G1 check, still asynchronous."""
+        _chk(lib().kzgx_verify_cells_each_checked_device(
+            self.h, d_commits, d_commit_inf, n_commits, d_commit_index, d_cell_index, d_proofs, d_proof_inf, d_ys,
+            count, log2n, log2l, _cosets_flags(extended, bitrev=bitrev), int(bool(subgroup)), d_ok, stream),
+            "kzgx_verify_cells_each_checked_device")
+
+    def set_verify_cells_chunk(self, cells: int) -> None:
+        """cells per internal chunk of verify_cells_each (0 = the default; at most 65535)"""
+        _chk(lib().kzgx_set_verify_cells_chunk(self.h, cells), "kzgx_set_verify_cells_chunk")
 
     # ---- compressed points ----
     def _records(self, data, rb) -> np.ndarray:

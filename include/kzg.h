@@ -390,6 +390,36 @@ class trusted_setup {
   std::pair<std::vector<Fr>, std::vector<proof>> recover_cells_and_proofs(
       const std::vector<uint32_t>& cell_index, const std::vector<std::vector<Fr>>& values, unsigned log2n,
       bool bit_reversed = false);
+  /** Extension: blob proofs (kzgx_prove_blobs_batch; BLS12-381 only).  `blobs`
+   *  holds whole blobs back to back, 2^log2n elements of 32 big-endian bytes
+   *  each, the values of a polynomial on the size-2^log2n domain (bit-reversed
+   *  order by default, as data-availability blobs come).  Returns the
+   *  commitments and the proofs as 48-byte KZGX_ENC_ZCASH records, back to
+   *  back: proof b opens blob b at its Fiat-Shamir challenge
+   *  z = H(blob || commitment) (kzg_gpu.h "blob proofs" has the layout).  One
+   *  batched GPU pipeline for all blobs.
+   *  @throws std::invalid_argument on BN254, a size that is not a whole number
+   *          of blobs, an element >= r, more than 65535 blobs, a domain beyond
+   *          the curve's or the setup */
+  std::pair<std::vector<uint8_t>, std::vector<uint8_t>> create_blob_proofs(const std::vector<uint8_t>& blobs,
+                                                                           unsigned log2n, bool bit_reversed = true);
+  /** Extension: one answer for all blobs (kzgx_verify_blobs_batch): records
+   *  decompressed and checked (with check_subgroup in the prime-order
+   *  subgroup), challenges hashed and values evaluated on the GPU, then ONE
+   *  pairing check under library-drawn 128-bit challenges.  False when a record
+   *  does not decode or an element is >= r.  No blobs: true.
+   *  @throws std::invalid_argument on BN254, mismatched sizes, too many blobs
+   *          (KZGX_MSM_POINTS_MAX / 2 - 1) or a domain beyond the curve's */
+  bool verify_blob_proofs(const std::vector<uint8_t>& blobs, const std::vector<uint8_t>& commits,
+                          const std::vector<uint8_t>& proofs, unsigned log2n, bool bit_reversed = true,
+                          bool check_subgroup = true);
+  /** Extension: the same batch, one exact verdict per blob
+   *  (kzgx_verify_blobs_each): a blob whose own record or element is invalid
+   *  is false and no other blob is affected.
+   *  @throws as verify_blob_proofs */
+  std::vector<bool> verify_blob_proofs_each(const std::vector<uint8_t>& blobs, const std::vector<uint8_t>& commits,
+                                            const std::vector<uint8_t>& proofs, unsigned log2n,
+                                            bool bit_reversed = true, bool check_subgroup = true);
   /** Extension: every installed G1 and G2 point is canonical, on its curve
    *  and (subgroup) in the prime-order subgroup (kzgx_srs_check, on the
    *  device).  trusted_setup(filename) tests on-curve only: call this after

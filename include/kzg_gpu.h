@@ -26,7 +26,12 @@
  * kzgx_prove_cosets_*, kzgx_coset_points: one opening per coset (cell) of that
  * domain or of the twice larger one, all cosets at once;
  * kzgx_verify_cells_aggregate*: one pairing check for many such cells;
- * kzgx_verify_cells_each*: one verdict per cell of such a batch.
+ * kzgx_verify_cells_each*: one verdict per cell of such a batch;
+ * kzgx_sha256, kzgx_blob_challenge(s), kzgx_evals_at_batch*, kzgx_prove_blobs_batch*,
+ * kzgx_verify_blobs_batch*, kzgx_verify_blobs_each* (flag KZGX_BLOB_BYTES): blob proofs --
+ * the Fiat-Shamir challenge of a blob hashed on the device, the value of an
+ * evaluation-form polynomial at any point, and blob-level prove / verify on 32-byte
+ * big-endian scalars and compressed points.
  *
  * Conventions
  *   - plain pointers and sizes only; no torch / HIP types in signatures
@@ -957,6 +962,138 @@ int kzgx_recover_cells_and_proofs_device(kzgx_ctx* ctx, const void* d_blob_index
                                          unsigned log2l, int flags, void* d_out_y, void* d_out_coeffs,
                                          void* d_out_proofs_xy, void* d_out_proofs_is_inf, void* d_ok,
                                          void* stream);
+
+/* ---- blob proofs (extension) --------------------------------------------------------------
+ * The blob-level half of the data-availability path (EIP-4844's compute_blob_kzg_proof and
+ * verify_blob_kzg_proof(_batch)): a blob's proof opens its polynomial at the Fiat-Shamir
+ * challenge z = H(blob || commitment), so the hash, the value y = P(z) and the byte-level
+ * scalar encoding all run on the device.  BLS12-381 only: every entry below returns
+ * KZGX_ERR_ARG on BN254 (no usable domain, no ZCash encoding).  No reference counterpart.
+ *  Blobs: n = 2^log2n field elements each, packed, the values of P_b (degree < n) on the
+ *   size-n domain of kzgx_domain_root(curve, log2n), in natural order or, with
+ *   KZGX_NTT_BITREV, in bit-reversed order (Ethereum's).  Default encoding: the library's
+ *   scalars (4 x uint64 little-endian limbs, canonical, taken as such).  With
+ *   KZGX_BLOB_BYTES: 32 n bytes, element i at bytes [32 i, 32 i + 32), big-endian, each
+ *   < r; a blob with any element >= r is INVALID, although the value is congruent to a
+ *   valid one.
+ *  Commitments and proofs are KZGX_ENC_ZCASH G1 records (48 bytes).
+ *  Challenge of (blob, commitment record): z = int_be(SHA-256(M)) mod r with
+ *   M = "FSBLOBVERIFY_V1_" (16 bytes) || n as 16-byte big-endian || the blob's 32 n bytes
+ *   || the 48-byte record, the blob's bytes being each element as 32-byte big-endian in the
+ *   order given (formed in registers from limbs).  |M| = 80 + 32 n; 2^256 div r = 2, so the
+ *   reduction subtracts r zero, one or two times.  kzgx_blob_challenge is the executable
+ *   statement of this layout.
+ *  Value: y = P(z) = (z^n - 1) / n  sum_i f_i w^i / (z - w^i) on the order given; when z
+ *   is the domain point w^i, y is exactly f_i.  The same canonical limbs as the y of
+ *   kzgx_prove_evals_batch.
+ *  Kernels (csrc/blob.hip, DESIGN.md "Blob proofs"): the challenge is one lane per blob,
+ *   a serial chain of (80 + 32 n) / 64 + 1 compressions, range-checking each element on the
+ *   way; the value is one workgroup per (polynomial, point), each lane folding its strided
+ *   slice of the n terms into one fraction (three products a term, no inversion), the
+ *   fractions added pairwise through LDS, and ONE Fermat inversion per value in a second
+ *   launch, one lane per value.
+ *  Device pointers to blobs, z and y must be 16-byte aligned (KZGX_ERR_ARG otherwise), as
+ *   scalar arrays are read and written 16 bytes at a time.
+ *  When it pays (BLS12-381, MI355X, profiles/blob_proofs.json, DESIGN.md "Blob proofs"; n =
+ *   4096, bit-reversed bytes, device pointers, 1 / 8 / 64 / 2048 blobs):
+ *   - the challenge kernel takes 7.2 to 8.0 ms WHATEVER the count (2050 dependent
+ *     compressions per lane): against a device-to-host copy of the blobs plus a host SHA-256
+ *     (0.11 / 0.63 / 4.9 / 224 ms of wall clock) it is SLOWER for 1, 8 and 64 blobs (x74, x13,
+ *     x1.5) and x29 faster at 2048; the crossover is near a hundred blobs;
+ *   - kzgx_evals_at_batch_device takes 0.55 / 0.51 / 0.48 / 0.87 ms against 0.17 / 0.27 / 0.28 /
+ *     1.28 ms for kzgx_ntt_device (inverse) + kzgx_quotient_single_batch_device: SLOWER below
+ *     about a thousand values (one workgroup and one Fermat inversion per value: a 0.5 ms
+ *     floor), x0.68 at 2048, and it needs neither limbs nor that route's two count x n buffers;
+ *   - kzgx_verify_blobs_batch_device takes 16.3 / 18.1 / 18.2 / 18.8 ms against 7.2 / 9.6 / 9.9 /
+ *     10.0 ms for kzgx_verify_aggregate_checked_device with z and y supplied (x2.25 .. x1.83):
+ *     the hash is the difference;
+ *   - kzgx_prove_blobs_batch_device takes 8.8 / 9.9 / 17.6 / 80.4 ms against 0.94 / 1.83 / 10.0 /
+ *     66.4 ms for kzgx_commit_evals_batch_device + kzgx_prove_evals_batch_device with z
+ *     supplied (x9.4, x5.4, x1.76, x1.21).
+ *   A caller with a handful of blobs already on the host should hash there.  No path is
+ *   chosen silently: every entry always runs the device path.
+ *  Statuses (every entry): BN254, an unknown flag, a NULL required pointer, log2n >
+ *   kzgx_ntt_max_log2(curve), NULL challenges on a device entry: KZGX_ERR_ARG, raised
+ *   before any device work. */
+#define KZGX_BLOB_BYTES 16 /* blob elements are 32-byte big-endian, checked < r */
+#define KZGX_BLOB_CHUNK_SCALARS 2097152
+/* Host utilities, no device and no context.  kzgx_sha256: the SHA-256 digest of len
+ * bytes.  kzgx_blob_challenge: z (4 x uint64) of one blob and one 48-byte record, host
+ * arithmetic; flags: KZGX_BLOB_BYTES only (the order is the order given, so
+ * KZGX_NTT_BITREV is accepted and changes nothing); *ok_out = 0 iff an element is >= r
+ * (always 1 for limbs) -- z is then still the hash of the bytes as given. */
+int kzgx_sha256(const uint8_t* msg, size_t len, uint8_t out[32]);
+int kzgx_blob_challenge(int curve, const void* blob, unsigned log2n, int flags, const uint8_t* commit_record,
+                        uint64_t* z_out, int* ok_out);
+/* count blobs + count records -> z (count x 4 uint64) and ok (count flags; may be NULL).
+ * No SRS is needed.  flags as kzgx_blob_challenge.  count == 0: KZGX_OK.  Device form:
+ * device pointers, d_ok count x uint32, asynchronous on stream (NULL = the context's). */
+int kzgx_blob_challenges(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags,
+                         const uint8_t* commit_records, uint64_t* z_out, int* ok_out);
+int kzgx_blob_challenges_device(kzgx_ctx* ctx, const void* d_blobs, unsigned log2n, size_t count, int flags,
+                                const void* d_commit_records, void* d_z, void* d_ok, void* stream);
+/* y_k = P_k(z_k), k < count, for polynomials given by their evaluations: polynomial k at
+ * evals + k * eval_stride elements (eval_stride == 0: one shared polynomial; else >= n;
+ * the host form copies (count - 1) eval_stride + n elements).  flags: KZGX_NTT_BITREV,
+ * KZGX_BLOB_BYTES.  No SRS is needed.  With KZGX_BLOB_BYTES the elements are NOT checked
+ * here (an element >= r is used reduced); kzgx_blob_challenges reports canonicity.
+ * Replaces, for a verifier, the inverse NTT into a coefficient buffer plus
+ * kzgx_quotient_single_batch_device with the quotient discarded. */
+int kzgx_evals_at_batch(kzgx_ctx* ctx, const void* evals, unsigned log2n, size_t eval_stride, const uint64_t* zs,
+                        size_t count, int flags, uint64_t* ys);
+int kzgx_evals_at_batch_device(kzgx_ctx* ctx, const void* d_evals, unsigned log2n, size_t eval_stride,
+                               const void* d_z, size_t count, int flags, void* d_y, void* stream);
+/* blobs -> commitment records and proof records (count x 48 bytes each), optionally the
+ * challenges z and the values y (count x 4 uint64; either may be NULL).  Pipeline, in
+ * chunks of max(1, KZGX_BLOB_CHUNK_SCALARS / n) blobs: [decode, KZGX_BLOB_BYTES only] ->
+ * kzgx_commit_evals_batch_device -> compress for every chunk; ONE challenge launch for the
+ * whole call (the hash takes as long for one blob as for thousands); then [decode] ->
+ * kzgx_prove_evals_batch_device at z -> compress for every chunk.  The workspace per
+ * stream is bounded by the chunk plus 36 bytes per blob of the call.
+ *  An invalid blob (KZGX_BLOB_BYTES, an element >= r): on the device form the identity
+ *   record for both outputs, ok[b] = 0 (d_ok: count x uint32, may be NULL), y = 0 and z the
+ *   hash of the bytes as given with the identity record; its neighbours are unaffected.  On
+ *   the host form KZGX_ERR_ARG (the outputs are then unspecified).
+ *  A caller who already holds the commitments composes kzgx_blob_challenges_device with
+ *   kzgx_prove_evals_batch_device and pays no second commit.
+ *  Statuses: count > 65535 (the prove path's batch limit): KZGX_ERR_ARG; no SRS:
+ *   KZGX_ERR_NO_SRS; 2^log2n larger than the installed SRS: KZGX_ERR_DEGREE; count == 0:
+ *   KZGX_OK. */
+int kzgx_prove_blobs_batch(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags,
+                           uint8_t* commit_records, uint8_t* proof_records, uint64_t* z_out, uint64_t* y_out);
+int kzgx_prove_blobs_batch_device(kzgx_ctx* ctx, const void* d_blobs, unsigned log2n, size_t count, int flags,
+                                  void* d_commit_records, void* d_proof_records, void* d_z, void* d_y, void* d_ok,
+                                  void* stream);
+/* One answer for count (blob, commitment record, proof record) triples with challenges r_k:
+ * exactly kzgx_verify_aggregate's equation on (C_k, pi_k, z_k, y_k, r_k), z_k and y_k as
+ * defined above, ANDed with "every record decodes (and, with subgroup != 0, lies in the
+ * order-r subgroup) and every element is canonical".  Pipeline: ONE decompress-and-check
+ * launch over both record arrays (as kzgx_verify_cells_aggregate_bytes), the challenges,
+ * the values, the unchanged kzgx_verify_aggregate_device, and the AND of all decode and
+ * canonical flags folded on the device: the device form stays asynchronous.
+ *  challenges: count x 4 uint64 canonical scalars.  The library does not hash to get them
+ *   (a verifier's randomness need not be Fiat-Shamir): explicit challenges give a
+ *   deterministic answer; NULL on the host entry draws 128-bit values as
+ *   kzgx_verify_aggregate does; NULL on the device entry is KZGX_ERR_ARG.
+ *  Needs G1[0] and G2[0..1] only (else KZGX_ERR_NO_SRS): 2^log2n may exceed the SRS.
+ *  count == 0 gives *ok = 1; count > KZGX_MSM_POINTS_MAX / 2 - 1: KZGX_ERR_ARG.  d_ok: one
+ *   uint32. */
+int kzgx_verify_blobs_batch(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags,
+                            const uint8_t* commit_records, const uint8_t* proof_records, const uint64_t* challenges,
+                            int subgroup, int* ok);
+int kzgx_verify_blobs_batch_device(kzgx_ctx* ctx, const void* d_blobs, unsigned log2n, size_t count, int flags,
+                                   const void* d_commit_records, const void* d_proof_records,
+                                   const void* d_challenges, int subgroup, void* d_ok, void* stream);
+/* The same front end, then kzgx_verify_single_batch_device: one verdict per blob (ok /
+ * d_ok: count entries), no challenges.  A blob whose own record does not decode (or fails
+ * the subgroup test) or that has an element >= r gets 0; no other blob is affected.  Errors
+ * that cancel in the aggregate under equal challenges are reported separately here.
+ * count == 0: KZGX_OK, nothing is written.  Limits as kzgx_verify_blobs_batch. */
+int kzgx_verify_blobs_each(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags,
+                           const uint8_t* commit_records, const uint8_t* proof_records, int subgroup, int* ok);
+int kzgx_verify_blobs_each_device(kzgx_ctx* ctx, const void* d_blobs, unsigned log2n, size_t count, int flags,
+                                  const void* d_commit_records, const void* d_proof_records, int subgroup,
+                                  void* d_ok, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1175,6 +1175,58 @@ std::pair<std::vector<Fr>, std::vector<proof>> trusted_setup::recover_cells_and_
   return {std::move(y), std::move(proofs)};
 }
 
+namespace {
+// blobs of 2^log2n 32-byte elements back to back: how many
+size_t blob_count(const std::vector<uint8_t>& blobs, unsigned log2n, const char* where) {
+  if (log2n > 31 || (int)log2n > kzgx_ntt_max_log2(g_curve))
+    throw std::invalid_argument(std::string(where) + ": the domain exceeds the curve's power-of-two domain");
+  const size_t bb = (size_t)32 << log2n;
+  if (blobs.size() % bb) throw std::invalid_argument(std::string(where) + ": not a whole number of blobs");
+  return blobs.size() / bb;
+}
+}  // namespace
+
+std::pair<std::vector<uint8_t>, std::vector<uint8_t>> trusted_setup::create_blob_proofs(
+    const std::vector<uint8_t>& blobs, unsigned log2n, bool bit_reversed) {
+  const size_t m = blob_count(blobs, log2n, "create_blob_proofs");
+  std::vector<uint8_t> commits(48 * m), proofs(48 * m);
+  const int flags = KZGX_BLOB_BYTES | (bit_reversed ? KZGX_NTT_BITREV : 0);
+  check(kzgx_prove_blobs_batch(ctx, blobs.data(), log2n, m, flags, commits.data(), proofs.data(), nullptr, nullptr),
+        "kzgx_prove_blobs_batch");
+  return {std::move(commits), std::move(proofs)};
+}
+
+bool trusted_setup::verify_blob_proofs(const std::vector<uint8_t>& blobs, const std::vector<uint8_t>& commits,
+                                       const std::vector<uint8_t>& proofs, unsigned log2n, bool bit_reversed,
+                                       bool check_subgroup) {
+  const size_t m = blob_count(blobs, log2n, "verify_blob_proofs");
+  if (commits.size() != 48 * m || proofs.size() != 48 * m)
+    throw std::invalid_argument("verify_blob_proofs: size mismatch");
+  const int flags = KZGX_BLOB_BYTES | (bit_reversed ? KZGX_NTT_BITREV : 0);
+  int ok = 0;
+  check(kzgx_verify_blobs_batch(ctx, blobs.data(), log2n, m, flags, commits.data(), proofs.data(), nullptr,
+                                check_subgroup ? 1 : 0, &ok),
+        "kzgx_verify_blobs_batch");
+  return ok != 0;
+}
+
+std::vector<bool> trusted_setup::verify_blob_proofs_each(const std::vector<uint8_t>& blobs,
+                                                         const std::vector<uint8_t>& commits,
+                                                         const std::vector<uint8_t>& proofs, unsigned log2n,
+                                                         bool bit_reversed, bool check_subgroup) {
+  const size_t m = blob_count(blobs, log2n, "verify_blob_proofs_each");
+  if (commits.size() != 48 * m || proofs.size() != 48 * m)
+    throw std::invalid_argument("verify_blob_proofs_each: size mismatch");
+  const int flags = KZGX_BLOB_BYTES | (bit_reversed ? KZGX_NTT_BITREV : 0);
+  std::vector<int> oks(m ? m : 1, 0);
+  check(kzgx_verify_blobs_each(ctx, blobs.data(), log2n, m, flags, commits.data(), proofs.data(),
+                               check_subgroup ? 1 : 0, oks.data()),
+        "kzgx_verify_blobs_each");
+  std::vector<bool> res;
+  for (size_t k = 0; k < m; k++) res.push_back(oks[k] != 0);
+  return res;
+}
+
 G1 trusted_setup::linear_combination(const std::vector<G1>& points, const std::vector<Fr>& scalars) {
   const size_t m = points.size();
   if (scalars.size() != m) throw std::invalid_argument("linear_combination: size mismatch");

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "blob.hpp"
 #include "curve_consts.h"
 #include "fr_host.hpp"
 #include "kzgx_internal.hpp"
@@ -58,6 +59,9 @@ struct kzgx_ctx {
   // slot of c.ws (so per stream, as the MSM workspaces are)
   uint32_t* d_chk[kzgx::KZGX_MAX_STREAMS] = {};
   size_t chk_b[kzgx::KZGX_MAX_STREAMS] = {};
+  // the blob entries' buffers (decoded limbs, recovered points, z, y, flags), per slot as d_chk
+  uint32_t* d_blob[kzgx::KZGX_MAX_STREAMS] = {};
+  size_t blob_b[kzgx::KZGX_MAX_STREAMS] = {};
 
   // pinned, device-mapped host staging for the host-pointer entry points
   // (kzgx_msm_g1_batch, kzgx_prove_single_batch): inputs are copied into it
@@ -614,6 +618,8 @@ void kzgx_destroy(kzgx_ctx* ctx) {
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->d_chk)
+    if (p) (void)hipFree(p);
+  for (void* p : ctx->d_blob)
     if (p) (void)hipFree(p);
   for (auto& f : c.fk) {
     if (f.x) (void)hipFree(f.x);
@@ -3120,6 +3126,336 @@ int kzgx_recover_cells_and_proofs(kzgx_ctx* ctx, const uint32_t* blob_index, con
                                   int* out_proofs_is_inf, int* ok) {
   return recover_host(ctx, blob_index, cell_index, ys, count, n_blobs, log2n, log2l, flags, out_y, out_coeffs, true,
                       out_proofs_xy, out_proofs_is_inf, ok);
+}
+
+}  // extern "C"
+
+// ---- blob proofs (blob.hip) -------------------------------------------------------------------
+namespace {
+// the checks every blob entry starts with: the curve, the flag bits, the domain
+int blob_args(int curve, unsigned log2n, int flags) {
+  if (curve != KZGX_CURVE_BLS12381 || (flags & ~(KZGX_NTT_BITREV | KZGX_BLOB_BYTES))) return KZGX_ERR_ARG;
+  return (int)log2n > kzgx::ntt_max_log2(curve) ? KZGX_ERR_ARG : KZGX_OK;
+}
+// scalar arrays are read and written 16 bytes at a time
+bool misaligned16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
+
+// the blob entries' buffer of the workspace slot leased for this call's stream
+int blob_scratch(kzgx_ctx* ctx, const kzgx::WsLease& ws, size_t bytes, uint8_t** out) {
+  const size_t slot = (size_t)(ws.get() - ctx->c.ws);
+  KZGX_TRY(kzgx::dev_alloc(&ctx->c, (void**)&ctx->d_blob[slot], bytes, &ctx->blob_b[slot]));
+  *out = (uint8_t*)ctx->d_blob[slot];
+  return KZGX_OK;
+}
+
+// library-drawn challenges: independent 128-bit values, r_0 = 1 (as kzgx_verify_aggregate)
+void draw_challenges(std::vector<uint64_t>& drawn, size_t count) {
+  drawn.assign(count * 4, 0);
+  std::random_device rd;
+  for (size_t k = 0; k < count; k++)
+    for (int j = 0; j < 2; j++) drawn[4 * k + j] = ((uint64_t)rd() << 32) | (uint64_t)rd();
+  drawn[0] = 1;
+  drawn[1] = 0;
+}
+
+// What both verify entries start with, in the slot's buffer: z | y | the value kernel's fractions |
+// the decoded commitments and proofs | their infinity flags | ok flags of the 2 count records and
+// the count blobs
+struct BlobFront {
+  uint32_t *z, *y, *xy, *inf, *okf;
+};
+int blob_verify_args(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags, const void* crec,
+                     const void* prec, const void* ok) {
+  KZGX_TRY(blob_args(ctx->c.curve, log2n, flags));
+  if (!ok || (count > 0 && (!blobs || !crec || !prec))) return KZGX_ERR_ARG;
+  if (count > KZGX_MSM_POINTS_MAX / 2 - 1) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0 || ctx->n_srs2 < 2) return KZGX_ERR_NO_SRS;
+  return KZGX_OK;
+}
+int blob_verify_front(kzgx_ctx* ctx, const kzgx::WsLease& ws, hipStream_t st, const void* d_blobs, unsigned log2n,
+                      size_t count, int flags, const void* d_crec, const void* d_prec, int subgroup, BlobFront* f) {
+  const size_t pw = point_words(ctx);
+  uint8_t* buf;
+  KZGX_TRY(blob_scratch(ctx, ws, count * (64 + kzgx::EVALS_AT_FRAC_BYTES + 2 * pw * 4 + 8 + 12) + 16, &buf));
+  f->z = (uint32_t*)buf;
+  f->y = f->z + count * 8;
+  uint32_t* frac = f->y + count * 8;
+  f->xy = frac + count * (kzgx::EVALS_AT_FRAC_BYTES / 4);
+  f->inf = f->xy + 2 * count * pw;
+  f->okf = f->inf + 2 * count;
+  KZGX_TRY(kzgx::g1_decompress2(&ctx->c, (const uint8_t*)d_crec, count, (const uint8_t*)d_prec, count, KZGX_ENC_ZCASH,
+                                subgroup, f->xy, f->inf, f->okf, st));
+  KZGX_TRY(kzgx::blob_challenges(&ctx->c, d_blobs, log2n, count, (flags & KZGX_BLOB_BYTES) != 0,
+                                 (const uint8_t*)d_crec, f->z, f->okf + 2 * count, st));
+  return kzgx::evals_at(&ctx->c, d_blobs, log2n, (size_t)1 << log2n, (flags & KZGX_BLOB_BYTES) != 0,
+                        (flags & KZGX_NTT_BITREV) != 0, f->z, count, f->y, frac, st);
+}
+
+// the host-pointer verify entries: blobs, records and challenges staged, one answer (each = false) or count
+int blob_verify_host(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags, const uint8_t* crec,
+                     const uint8_t* prec, const uint64_t* challenges, int subgroup, bool each, int* ok) {
+  KZGX_TRY(activate(ctx));
+  KZGX_TRY(blob_verify_args(ctx, blobs, log2n, count, flags, crec, prec, ok));
+  if (count == 0) {
+    if (!each) *ok = 1;
+    return KZGX_OK;
+  }
+  std::vector<uint64_t> drawn;
+  if (!each && !challenges) {
+    draw_challenges(drawn, count);
+    challenges = drawn.data();
+  }
+  const size_t bb = count * ((size_t)32 << log2n);
+  void *d_b, *d_r, *d_s, *d_f;
+  KZGX_TRY(stage(ctx, 0, bb, &d_b));
+  KZGX_TRY(stage(ctx, 1, 2 * count * 48, &d_r));  // commit records | proof records
+  KZGX_TRY(stage(ctx, 2, count * 32, &d_s));
+  KZGX_TRY(stage(ctx, 3, count * 4 + 16, &d_f));
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_b, blobs, bb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_r, crec, count * 48, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync((char*)d_r + count * 48, prec, count * 48, hipMemcpyHostToDevice, st));
+  std::vector<uint32_t> v(each ? count : 1);
+  if (each) {
+    KZGX_TRY(kzgx_verify_blobs_each_device(ctx, d_b, log2n, count, flags, d_r, (char*)d_r + count * 48, subgroup, d_f,
+                                           nullptr));
+  } else {
+    KZGX_TRY_HIP(hipMemcpyAsync(d_s, challenges, count * 32, hipMemcpyHostToDevice, st));
+    KZGX_TRY(kzgx_verify_blobs_batch_device(ctx, d_b, log2n, count, flags, d_r, (char*)d_r + count * 48, d_s, subgroup,
+                                            d_f, nullptr));
+  }
+  KZGX_TRY_HIP(hipMemcpyAsync(v.data(), d_f, v.size() * 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t k = 0; k < v.size(); k++) ok[k] = v[k] ? 1 : 0;
+  return KZGX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kzgx_sha256(const uint8_t* msg, size_t len, uint8_t out[32]) {
+  if (!out || (len > 0 && !msg)) return KZGX_ERR_ARG;
+  kzgx::sha256_host(msg, len, out);
+  return KZGX_OK;
+}
+
+int kzgx_blob_challenge(int curve, const void* blob, unsigned log2n, int flags, const uint8_t* commit_record,
+                        uint64_t* z_out, int* ok_out) {
+  KZGX_TRY(blob_args(curve, log2n, flags));
+  if (!blob || !commit_record || !z_out) return KZGX_ERR_ARG;
+  kzgx::blob_challenge_host(blob, log2n, (flags & KZGX_BLOB_BYTES) != 0, commit_record, z_out, ok_out);
+  return KZGX_OK;
+}
+
+int kzgx_blob_challenges_device(kzgx_ctx* ctx, const void* d_blobs, unsigned log2n, size_t count, int flags,
+                                const void* d_commit_records, void* d_z, void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  KZGX_TRY(blob_args(ctx->c.curve, log2n, flags));
+  if (count == 0) return KZGX_OK;
+  if (!d_blobs || !d_commit_records || !d_z || misaligned16(d_blobs) || misaligned16(d_z)) return KZGX_ERR_ARG;
+  return kzgx::blob_challenges(&ctx->c, d_blobs, log2n, count, (flags & KZGX_BLOB_BYTES) != 0,
+                               (const uint8_t*)d_commit_records, (uint32_t*)d_z, (uint32_t*)d_ok, pick(ctx, stream));
+}
+
+int kzgx_blob_challenges(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags,
+                         const uint8_t* commit_records, uint64_t* z_out, int* ok_out) {
+  KZGX_TRY(activate(ctx));
+  KZGX_TRY(blob_args(ctx->c.curve, log2n, flags));
+  if (count == 0) return KZGX_OK;
+  if (!blobs || !commit_records || !z_out || count > 0x7fffffffu) return KZGX_ERR_ARG;
+  const size_t bb = count * ((size_t)32 << log2n);
+  void *d_b, *d_r, *d_o;
+  KZGX_TRY(stage(ctx, 0, bb, &d_b));
+  KZGX_TRY(stage(ctx, 1, count * 48, &d_r));
+  KZGX_TRY(stage(ctx, 2, count * 36, &d_o));  // z | ok
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_b, blobs, bb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_r, commit_records, count * 48, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx_blob_challenges_device(ctx, d_b, log2n, count, flags, d_r, d_o, (char*)d_o + count * 32, st));
+  std::vector<uint32_t> f(count);
+  KZGX_TRY_HIP(hipMemcpyAsync(z_out, d_o, count * 32, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(f.data(), (char*)d_o + count * 32, count * 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  flags_out(f, 0, count, ok_out);
+  return KZGX_OK;
+}
+
+int kzgx_evals_at_batch_device(kzgx_ctx* ctx, const void* d_evals, unsigned log2n, size_t eval_stride,
+                               const void* d_z, size_t count, int flags, void* d_y, void* stream) {
+  KZGX_TRY(activate(ctx));
+  KZGX_TRY(blob_args(ctx->c.curve, log2n, flags));
+  if (eval_stride != 0 && eval_stride < ((size_t)1 << log2n)) return KZGX_ERR_ARG;
+  if (count == 0) return KZGX_OK;
+  if (!d_evals || !d_z || !d_y || misaligned16(d_evals) || misaligned16(d_z) || misaligned16(d_y) ||
+      count > 0x7fffffffu)
+    return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  uint8_t* frac;
+  KZGX_TRY(blob_scratch(ctx, ws, count * kzgx::EVALS_AT_FRAC_BYTES, &frac));
+  return kzgx::evals_at(&ctx->c, d_evals, log2n, eval_stride, (flags & KZGX_BLOB_BYTES) != 0,
+                        (flags & KZGX_NTT_BITREV) != 0, (const uint32_t*)d_z, count, (uint32_t*)d_y, (uint32_t*)frac,
+                        st);
+}
+
+int kzgx_evals_at_batch(kzgx_ctx* ctx, const void* evals, unsigned log2n, size_t eval_stride, const uint64_t* zs,
+                        size_t count, int flags, uint64_t* ys) {
+  KZGX_TRY(activate(ctx));
+  KZGX_TRY(blob_args(ctx->c.curve, log2n, flags));
+  const size_t n = (size_t)1 << log2n;
+  if (eval_stride != 0 && eval_stride < n) return KZGX_ERR_ARG;
+  if (count == 0) return KZGX_OK;
+  if (!evals || !zs || !ys || count > 0x7fffffffu) return KZGX_ERR_ARG;
+  const size_t eb = ((count - 1) * eval_stride + n) * 32;
+  void *d_e, *d_s;
+  KZGX_TRY(stage(ctx, 0, eb, &d_e));
+  KZGX_TRY(stage(ctx, 1, count * 64, &d_s));  // z | y
+  hipStream_t st = ctx->c.stream;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_e, evals, eb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_s, zs, count * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx_evals_at_batch_device(ctx, d_e, log2n, eval_stride, d_s, count, flags, (char*)d_s + count * 32, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(ys, (char*)d_s + count * 32, count * 32, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  return KZGX_OK;
+}
+
+int kzgx_prove_blobs_batch_device(kzgx_ctx* ctx, const void* d_blobs, unsigned log2n, size_t count, int flags,
+                                  void* d_commit_records, void* d_proof_records, void* d_z, void* d_y, void* d_ok,
+                                  void* stream) {
+  KZGX_TRY(activate(ctx));
+  KZGX_TRY(blob_args(ctx->c.curve, log2n, flags));
+  if (count == 0) return KZGX_OK;
+  if (!d_blobs || !d_commit_records || !d_proof_records || misaligned16(d_blobs) || misaligned16(d_z) ||
+      misaligned16(d_y) || count > 65535)
+    return KZGX_ERR_ARG;
+  const size_t n = (size_t)1 << log2n;
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  if (n > ctx->c.n_srs) return KZGX_ERR_DEGREE;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::Ctx* c = &ctx->c;
+  kzgx::WsLease ws = c->ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const bool bytes = (flags & KZGX_BLOB_BYTES) != 0;
+  const int nflags = flags & KZGX_NTT_BITREV;
+  const size_t per = std::min(count, std::max<size_t>(1, kzgx::BLOB_CHUNK_SCALARS >> log2n)), pw = point_words(ctx);
+  // a chunk's decoded limbs | its y | its points | their infinity flags | every blob's z | every blob's ok flag
+  const size_t o_y = bytes ? per * n * 32 : 0, o_p = o_y + per * 32, o_i = o_p + per * pw * 4, o_z = o_i + per * 16,
+               o_k = o_z + count * 32;
+  uint8_t* buf;
+  KZGX_TRY(blob_scratch(ctx, ws, o_k + count * 4, &buf));
+  uint32_t* pts = (uint32_t*)(buf + o_p);
+  uint32_t* inf = (uint32_t*)(buf + o_i);
+  uint32_t* z = d_z ? (uint32_t*)d_z : (uint32_t*)(buf + o_z);
+  uint32_t* okf = d_ok ? (uint32_t*)d_ok : (uint32_t*)(buf + o_k);
+  // Two passes over the chunks with ONE challenge launch between them: the hash is a serial chain per lane
+  // that takes as long for one blob as for thousands, so it is paid once per call, not once per chunk.
+  // A call of several chunks decodes each chunk twice (a pass over its bytes) to keep the workspace bounded.
+  for (int pass = 0; pass < 2; pass++) {
+    for (size_t b0 = 0; b0 < count; b0 += per) {
+      const size_t cb = std::min(per, count - b0);
+      const uint8_t* src = (const uint8_t*)d_blobs + b0 * n * 32;
+      const void* evals = src;
+      if (bytes) {  // an invalid blob decodes to the zero polynomial: both records the identity
+        if (pass == 0 || count > per) KZGX_TRY(kzgx::blob_decode(c, src, log2n, cb, (uint32_t*)buf, okf + b0, st));
+        evals = buf;
+      }
+      uint8_t* rec = (uint8_t*)(pass == 0 ? d_commit_records : d_proof_records) + b0 * 48;
+      if (pass == 0) {
+        KZGX_TRY(kzgx_commit_evals_batch_device(ctx, evals, log2n, cb, n, nflags, pts, inf, st));
+      } else {
+        uint32_t* yp = d_y ? (uint32_t*)d_y + b0 * 8 : (uint32_t*)(buf + o_y);
+        KZGX_TRY(kzgx_prove_evals_batch_device(ctx, evals, log2n, n, z + b0 * 8, cb, nflags, pts, inf, yp, st));
+      }
+      KZGX_TRY(kzgx::g1_compress(c, pts, inf, cb, KZGX_ENC_ZCASH, rec, st));
+    }
+    if (pass == 0)
+      KZGX_TRY(kzgx::blob_challenges(c, d_blobs, log2n, count, bytes, (const uint8_t*)d_commit_records, z, okf, st));
+  }
+  return KZGX_OK;
+}
+
+int kzgx_prove_blobs_batch(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags,
+                           uint8_t* commit_records, uint8_t* proof_records, uint64_t* z_out, uint64_t* y_out) {
+  KZGX_TRY(activate(ctx));
+  KZGX_TRY(blob_args(ctx->c.curve, log2n, flags));
+  if (count == 0) return KZGX_OK;
+  if (!blobs || !commit_records || !proof_records || count > 65535) return KZGX_ERR_ARG;
+  const size_t bb = count * ((size_t)32 << log2n);
+  const size_t o_p = count * 48, o_z = align256(2 * count * 48), o_y = o_z + count * 32, o_k = o_y + count * 32;
+  void *d_b, *d_o;
+  KZGX_TRY(stage(ctx, 0, bb, &d_b));
+  KZGX_TRY(stage(ctx, 1, o_k + count * 4, &d_o));
+  hipStream_t st = ctx->c.stream;
+  char* o = (char*)d_o;
+  KZGX_TRY_HIP(hipMemcpyAsync(d_b, blobs, bb, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx_prove_blobs_batch_device(ctx, d_b, log2n, count, flags, o, o + o_p, o + o_z, o + o_y, o + o_k, st));
+  std::vector<uint32_t> f(count);
+  KZGX_TRY_HIP(hipMemcpyAsync(commit_records, o, count * 48, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(proof_records, o + o_p, count * 48, hipMemcpyDeviceToHost, st));
+  if (z_out) KZGX_TRY_HIP(hipMemcpyAsync(z_out, o + o_z, count * 32, hipMemcpyDeviceToHost, st));
+  if (y_out) KZGX_TRY_HIP(hipMemcpyAsync(y_out, o + o_y, count * 32, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(f.data(), o + o_k, count * 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t b = 0; b < count; b++)
+    if (!f[b]) return KZGX_ERR_ARG;  // an element >= r
+  return KZGX_OK;
+}
+
+int kzgx_verify_blobs_batch_device(kzgx_ctx* ctx, const void* d_blobs, unsigned log2n, size_t count, int flags,
+                                   const void* d_commit_records, const void* d_proof_records,
+                                   const void* d_challenges, int subgroup, void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  KZGX_TRY(blob_verify_args(ctx, d_blobs, log2n, count, flags, d_commit_records, d_proof_records, d_ok));
+  if (!d_challenges || misaligned16(d_blobs)) return KZGX_ERR_ARG;
+  hipStream_t st = pick(ctx, stream);
+  if (count == 0) {
+    KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)d_ok, 1, 1, st));
+    return KZGX_OK;
+  }
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  BlobFront f;
+  KZGX_TRY(blob_verify_front(ctx, ws, st, d_blobs, log2n, count, flags, d_commit_records, d_proof_records, subgroup,
+                             &f));
+  uint32_t* all = f.okf + 3 * count;  // every record decodes and every blob is canonical
+  KZGX_TRY(kzgx::flags_and(f.okf, 3 * count, all, st));
+  const size_t pw = point_words(ctx);
+  KZGX_TRY(kzgx_verify_aggregate_device(ctx, f.xy, f.inf, f.xy + count * pw, f.inf + count, f.z, f.y, d_challenges,
+                                        count, d_ok, stream));
+  return kzgx::flag_gate((uint32_t*)d_ok, all, st);
+}
+
+int kzgx_verify_blobs_each_device(kzgx_ctx* ctx, const void* d_blobs, unsigned log2n, size_t count, int flags,
+                                  const void* d_commit_records, const void* d_proof_records, int subgroup,
+                                  void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  KZGX_TRY(blob_verify_args(ctx, d_blobs, log2n, count, flags, d_commit_records, d_proof_records, d_ok));
+  if (misaligned16(d_blobs)) return KZGX_ERR_ARG;
+  if (count == 0) return KZGX_OK;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::WsLease ws = ctx->c.ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  BlobFront f;
+  KZGX_TRY(blob_verify_front(ctx, ws, st, d_blobs, log2n, count, flags, d_commit_records, d_proof_records, subgroup,
+                             &f));
+  const size_t pw = point_words(ctx);
+  KZGX_TRY(kzgx_verify_single_batch_device(ctx, f.xy, f.inf, f.xy + count * pw, f.inf + count, f.z, f.y, count, d_ok,
+                                           stream));
+  // a blob's own records and elements gate its verdict, nobody else's
+  return kzgx::blob_gate((uint32_t*)d_ok, f.okf, f.okf + count, f.okf + 2 * count, count, st);
+}
+
+int kzgx_verify_blobs_batch(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags,
+                            const uint8_t* commit_records, const uint8_t* proof_records, const uint64_t* challenges,
+                            int subgroup, int* ok) {
+  return blob_verify_host(ctx, blobs, log2n, count, flags, commit_records, proof_records, challenges, subgroup, false,
+                          ok);
+}
+
+int kzgx_verify_blobs_each(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags,
+                           const uint8_t* commit_records, const uint8_t* proof_records, int subgroup, int* ok) {
+  return blob_verify_host(ctx, blobs, log2n, count, flags, commit_records, proof_records, nullptr, subgroup, true, ok);
 }
 
 }  // extern "C"

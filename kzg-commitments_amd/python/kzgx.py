@@ -51,6 +51,10 @@ EXPORTS = [
     "kzgx_point_bytes", "kzgx_g1_decompress_batch", "kzgx_g1_decompress_batch_device", "kzgx_g1_compress_batch",
     "kzgx_g1_compress_batch_device", "kzgx_g2_decompress_batch", "kzgx_g2_compress_batch",
     "kzgx_verify_cells_aggregate_bytes", "kzgx_verify_cells_aggregate_bytes_device",
+    "kzgx_sha256", "kzgx_blob_challenge", "kzgx_blob_challenges", "kzgx_blob_challenges_device",
+    "kzgx_evals_at_batch", "kzgx_evals_at_batch_device", "kzgx_prove_blobs_batch", "kzgx_prove_blobs_batch_device",
+    "kzgx_verify_blobs_batch", "kzgx_verify_blobs_batch_device", "kzgx_verify_blobs_each",
+    "kzgx_verify_blobs_each_device",
 ]
 
 
@@ -79,6 +83,9 @@ RECOVER_CHUNK_SCALARS = _header_define("KZGX_RECOVER_CHUNK_SCALARS")
 # compressed points: the ZCash / IETF BLS12-381 encoding, and SEC1 (0x02 | parity, then x)
 ENC_ZCASH = _header_define("KZGX_ENC_ZCASH")
 ENC_SEC1 = _header_define("KZGX_ENC_SEC1")
+# blob proofs: elements are 32-byte big-endian (checked < r), and the scalars per internal chunk of blobs
+BLOB_BYTES = _header_define("KZGX_BLOB_BYTES")
+BLOB_CHUNK_SCALARS = _header_define("KZGX_BLOB_CHUNK_SCALARS")
 
 _lib = None
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -259,6 +266,23 @@ def lib():
             "kzgx_verify_cells_aggregate_bytes_device": (ctypes.c_int, [vp, vp, sz, vp, vp, vp, vp, vp, sz,
                                                                         ctypes.c_uint, ctypes.c_uint, ctypes.c_int,
                                                                         ctypes.c_int, ctypes.c_int, vp, vp]),
+            "kzgx_sha256": (ctypes.c_int, [u8p, sz, u8p]),
+            "kzgx_blob_challenge": (ctypes.c_int, [ctypes.c_int, vp, ctypes.c_uint, ctypes.c_int, u8p, u64p, intp]),
+            "kzgx_blob_challenges": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, ctypes.c_int, u8p, u64p, intp]),
+            "kzgx_blob_challenges_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, ctypes.c_int, vp, vp, vp, vp]),
+            "kzgx_evals_at_batch": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, u64p, sz, ctypes.c_int, u64p]),
+            "kzgx_evals_at_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, vp, sz, ctypes.c_int, vp, vp]),
+            "kzgx_prove_blobs_batch": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, ctypes.c_int, u8p, u8p, u64p, u64p]),
+            "kzgx_prove_blobs_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, ctypes.c_int, vp, vp, vp, vp,
+                                                             vp, vp]),
+            "kzgx_verify_blobs_batch": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, ctypes.c_int, u8p, u8p, u64p,
+                                                       ctypes.c_int, intp]),
+            "kzgx_verify_blobs_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, ctypes.c_int, vp, vp, vp,
+                                                              ctypes.c_int, vp, vp]),
+            "kzgx_verify_blobs_each": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, ctypes.c_int, u8p, u8p, ctypes.c_int,
+                                                      intp]),
+            "kzgx_verify_blobs_each_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, ctypes.c_int, vp, vp,
+                                                             ctypes.c_int, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -354,6 +378,60 @@ def coset_points(curve: str, log2n: int, log2l: int, index: int, extended: bool 
     _chk(lib().kzgx_coset_points(CURVES[curve], log2n, log2l, _cosets_flags(extended, bitrev=bitrev), index, _p(xs)),
          "kzgx_coset_points")
     return xs
+
+
+def _blob_flags(bytes_mode: bool = False, bitrev: bool = False) -> int:
+    return (BLOB_BYTES if bytes_mode else 0) | _ntt_flags(bitrev=bitrev)
+
+
+def _blob_array(blobs, log2n: int):
+    """blobs as one contiguous array: bytes / bytearray / a uint8 array are 32-byte big-endian elements
+    (KZGX_BLOB_BYTES), anything else (.., 4) uint64 limbs -> (array, bytes_mode, count)"""
+    if isinstance(blobs, (bytes, bytearray)):
+        blobs = np.frombuffer(bytes(blobs), dtype=np.uint8)
+    a = np.asarray(blobs)
+    per = 32 << log2n
+    if a.dtype == np.uint8:
+        a = np.ascontiguousarray(a).reshape(-1)
+        assert a.shape[0] % per == 0
+        return a, True, a.shape[0] // per
+    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+    assert a.shape[0] % (1 << log2n) == 0
+    return a, False, a.shape[0] >> log2n
+
+
+def _records48(data) -> np.ndarray:
+    b = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else \
+        np.ascontiguousarray(data, dtype=np.uint8)
+    b = np.ascontiguousarray(b).reshape(-1)
+    assert b.shape[0] % 48 == 0
+    return b
+
+
+def sha256(data) -> bytes:
+    """kzgx_sha256: the SHA-256 digest (host arithmetic, no device)"""
+    m = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.zeros(32, dtype=np.uint8)
+    _chk(lib().kzgx_sha256(m.ctypes.data_as(u8p) if m.shape[0] else None, m.shape[0], out.ctypes.data_as(u8p)),
+         "kzgx_sha256")
+    return out.tobytes()
+
+
+def blob_challenge(curve: str, blob, record, flags: int | None = None):
+    """kzgx_blob_challenge: one blob (bytes: 32-byte big-endian elements; else (n, 4) uint64 limbs) and its 48-byte
+    commitment record -> (z as an integer, ok); host arithmetic, no device.  flags: None = from the blob's type."""
+    a = np.asarray(np.frombuffer(bytes(blob), dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
+    nel = a.size // 32 if a.dtype == np.uint8 else a.size // 4
+    log2n = _log2_exact(nel)
+    a, bm, cnt = _blob_array(a, log2n)
+    assert cnt == 1
+    rec = _records48(record)
+    assert rec.shape[0] == 48
+    z = np.zeros(4, dtype=np.uint64)
+    ok = ctypes.c_int(0)
+    _chk(lib().kzgx_blob_challenge(CURVES[curve], a.ctypes.data, log2n, _blob_flags(bm) if flags is None else flags,
+                                   rec.ctypes.data_as(u8p), _p(z), ctypes.byref(ok)), "kzgx_blob_challenge")
+    return sum(int(z[i]) << (64 * i) for i in range(4)), bool(ok.value)
 
 
 def _log2_exact(n: int) -> int:
@@ -1267,3 +1345,108 @@ class Context:
             self.h, d_blob_index, d_cell_index, d_ys, count, n_blobs, log2n, log2l,
             _cosets_flags(extended, bitrev=bitrev), d_out_y, d_out_coeffs, d_out_xy, d_out_inf, d_ok, stream),
             "kzgx_recover_cells_and_proofs_device")
+
+    # ---- blob proofs ----
+    def blob_challenges(self, blobs, log2n, records, bitrev: bool = False):
+        """kzgx_blob_challenges: count blobs (bytes / uint8: 32-byte big-endian elements; else uint64 limbs) and
+        count 48-byte commitment records -> (z (count, 4) uint64, ok (count,) bool); bitrev is accepted and changes
+        nothing (the order hashed is the order given)"""
+        a, bm, cnt = _blob_array(blobs, log2n)
+        rec = _records48(records)
+        assert rec.shape[0] == 48 * cnt
+        z = np.zeros((cnt, 4), dtype=np.uint64)
+        ok = np.zeros(cnt, dtype=np.int32)
+        _chk(lib().kzgx_blob_challenges(self.h, a.ctypes.data if cnt else None, log2n, cnt, _blob_flags(bm, bitrev),
+                                        rec.ctypes.data_as(u8p) if cnt else None, _p(z), ok.ctypes.data_as(intp)),
+             "kzgx_blob_challenges")
+        return z, ok.astype(bool)
+
+    def blob_challenges_device(self, d_blobs, log2n, count, d_records, d_z, d_ok, bytes_mode=False, bitrev=False,
+                               stream=None):
+        """kzgx_blob_challenges_device: device pointers (d_ok count uint32 or None), enqueued on stream."""
+        _chk(lib().kzgx_blob_challenges_device(self.h, d_blobs, log2n, count, _blob_flags(bytes_mode, bitrev),
+                                               d_records, d_z, d_ok, stream), "kzgx_blob_challenges_device")
+
+    def evals_at(self, evals, log2n, zs, shared: bool = False, bitrev: bool = False) -> np.ndarray:
+        """kzgx_evals_at_batch: y_k = P_k(z_k) for polynomials given by their 2^log2n evaluations (bytes / uint8 or
+        limbs as blob_challenges; shared: one polynomial for every z) -> (count, 4) uint64"""
+        a, bm, cnt = _blob_array(evals, log2n)
+        z = as_scalars(zs)
+        m = z.shape[0]
+        assert cnt == (1 if shared else m) or m == 0
+        y = np.zeros((m, 4), dtype=np.uint64)
+        _chk(lib().kzgx_evals_at_batch(self.h, a.ctypes.data if a.size else None, log2n, 0 if shared else 1 << log2n,
+                                       _p(z) if m else None, m, _blob_flags(bm, bitrev), _p(y)),
+             "kzgx_evals_at_batch")
+        return y
+
+    def evals_at_device(self, d_evals, log2n, stride, d_z, count, d_y, bytes_mode=False, bitrev=False, stream=None):
+        """kzgx_evals_at_batch_device: device pointers, stride in elements (0: shared), enqueued on stream."""
+        _chk(lib().kzgx_evals_at_batch_device(self.h, d_evals, log2n, stride, d_z, count,
+                                              _blob_flags(bytes_mode, bitrev), d_y, stream),
+             "kzgx_evals_at_batch_device")
+
+    def prove_blobs(self, blobs, log2n, bitrev: bool = False):
+        """kzgx_prove_blobs_batch: -> (commitment records, proof records (bytes, 48 per blob), z, y (count, 4));
+        an invalid blob raises KzgxError(KZGX_ERR_ARG)"""
+        a, bm, cnt = _blob_array(blobs, log2n)
+        c = np.zeros(48 * cnt, dtype=np.uint8)
+        p = np.zeros(48 * cnt, dtype=np.uint8)
+        z = np.zeros((cnt, 4), dtype=np.uint64)
+        y = np.zeros((cnt, 4), dtype=np.uint64)
+        _chk(lib().kzgx_prove_blobs_batch(self.h, a.ctypes.data if cnt else None, log2n, cnt, _blob_flags(bm, bitrev),
+                                          c.ctypes.data_as(u8p), p.ctypes.data_as(u8p), _p(z), _p(y)),
+             "kzgx_prove_blobs_batch")
+        return c.tobytes(), p.tobytes(), z, y
+
+    def prove_blobs_device(self, d_blobs, log2n, count, d_commits, d_proofs, d_z, d_y, d_ok, bytes_mode=False,
+                           bitrev=False, stream=None):
+        """kzgx_prove_blobs_batch_device: device pointers (d_z, d_y, d_ok may be None), enqueued on stream."""
+        _chk(lib().kzgx_prove_blobs_batch_device(self.h, d_blobs, log2n, count, _blob_flags(bytes_mode, bitrev),
+                                                 d_commits, d_proofs, d_z, d_y, d_ok, stream),
+             "kzgx_prove_blobs_batch_device")
+
+    def _verify_blobs_marshal(self, blobs, log2n, commits, proofs):
+        a, bm, cnt = _blob_array(blobs, log2n)
+        c, p = _records48(commits), _records48(proofs)
+        assert c.shape[0] == 48 * cnt and p.shape[0] == 48 * cnt
+        return a, bm, cnt, c, p
+
+    def verify_blobs(self, blobs, log2n, commits, proofs, challenges=None, bitrev: bool = False,
+                     subgroup: bool = False) -> bool:
+        """kzgx_verify_blobs_batch: one answer for count (blob, commitment record, proof record) triples;
+        challenges (count, 4) or None (library-drawn)"""
+        a, bm, cnt, c, p = self._verify_blobs_marshal(blobs, log2n, commits, proofs)
+        r = None if challenges is None or not cnt else as_scalars(challenges)
+        assert r is None or r.shape[0] == cnt
+        ok = ctypes.c_int(0)
+        _chk(lib().kzgx_verify_blobs_batch(self.h, a.ctypes.data if cnt else None, log2n, cnt, _blob_flags(bm, bitrev),
+                                           c.ctypes.data_as(u8p) if cnt else None,
+                                           p.ctypes.data_as(u8p) if cnt else None, None if r is None else _p(r),
+                                           int(bool(subgroup)), ctypes.byref(ok)), "kzgx_verify_blobs_batch")
+        return bool(ok.value)
+
+    def verify_blobs_each(self, blobs, log2n, commits, proofs, bitrev: bool = False,
+                          subgroup: bool = False) -> np.ndarray:
+        """kzgx_verify_blobs_each: one verdict per blob -> (count,) bool"""
+        a, bm, cnt, c, p = self._verify_blobs_marshal(blobs, log2n, commits, proofs)
+        ok = np.zeros(max(cnt, 1), dtype=np.int32)
+        _chk(lib().kzgx_verify_blobs_each(self.h, a.ctypes.data if cnt else None, log2n, cnt, _blob_flags(bm, bitrev),
+                                          c.ctypes.data_as(u8p) if cnt else None,
+                                          p.ctypes.data_as(u8p) if cnt else None, int(bool(subgroup)),
+                                          ok.ctypes.data_as(intp)), "kzgx_verify_blobs_each")
+        return ok[:cnt].astype(bool)
+
+    def verify_blobs_device(self, d_blobs, log2n, count, d_commits, d_proofs, d_challenges, subgroup, d_ok,
+                            bytes_mode=False, bitrev=False, stream=None):
+        """kzgx_verify_blobs_batch_device: device pointers, d_ok one uint32, still asynchronous."""
+        _chk(lib().kzgx_verify_blobs_batch_device(self.h, d_blobs, log2n, count, _blob_flags(bytes_mode, bitrev),
+                                                  d_commits, d_proofs, d_challenges, int(bool(subgroup)), d_ok,
+                                                  stream), "kzgx_verify_blobs_batch_device")
+
+    def verify_blobs_each_device(self, d_blobs, log2n, count, d_commits, d_proofs, subgroup, d_ok, bytes_mode=False,
+                                 bitrev=False, stream=None):
+        """kzgx_verify_blobs_each_device: device pointers, d_ok count uint32, still asynchronous."""
+        _chk(lib().kzgx_verify_blobs_each_device(self.h, d_blobs, log2n, count, _blob_flags(bytes_mode, bitrev),
+                                                 d_commits, d_proofs, int(bool(subgroup)), d_ok, stream),
+             "kzgx_verify_blobs_each_device")

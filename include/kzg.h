@@ -423,8 +423,28 @@ class trusted_setup {
   /** Extension: every installed G1 and G2 point is canonical, on its curve
    *  and (subgroup) in the prime-order subgroup (kzgx_srs_check, on the
    *  device).  trusted_setup(filename) tests on-curve only: call this after
-   *  loading a file you did not write. */
+   *  loading a file you did not write.  It tests each point on its own:
+   *  whether the points are consecutive powers of one tau is
+   *  verify_structure()'s question. */
   bool check_setup(bool subgroup = true);
+  /** Extension: one powers-of-tau contribution (kzgx_srs_update): point i of
+   *  both halves is multiplied by s^i on the GPU, so a setup for tau becomes
+   *  one for tau s, and every table and cached setup follows.  Returns the
+   *  witness [s]G2 that verify_contribution needs.  No transcript format, no
+   *  chain verifier, no hashing of s: s is the caller's to draw and forget.
+   *  @throws std::invalid_argument if s is zero */
+  G2 contribute(const Fr& s);
+  /** Extension: the installed points are consecutive powers of one tau in
+   *  both groups (kzgx_srs_verify_structure: two MSMs per group under random
+   *  challenges and two pairing equations), and with `generators` they start
+   *  at the curve's generators, as every setup this library generates does.
+   *  Meaningful only for subgroup members: call check_setup() first.  A wrong
+   *  setup passes with probability about size() / 2^128. */
+  bool verify_structure(bool generators = true);
+  /** Extension: e(new_tau, G2) == e(prev_tau, witness), witness and new_tau
+   *  finite (kzgx_srs_verify_update): new_tau = g1_points()[1] after a
+   *  contribution whose predecessor's was prev_tau. */
+  static bool verify_contribution(const G1& prev_tau, const G1& new_tau, const G2& witness);
   /** Extension: sum scalars[k] * points[k] on the GPU (kzgx_msm_g1_points).
    *  KZG commitments are additively homomorphic: the combination of
    *  commitments is the commitment of the combined polynomials.

@@ -1095,6 +1095,66 @@ int kzgx_verify_blobs_each_device(kzgx_ctx* ctx, const void* d_blobs, unsigned l
                                   const void* d_commit_records, const void* d_proof_records, int subgroup,
                                   void* d_ok, void* stream);
 
+/* ---- setup ceremony (extension) -----------------------------------------------------------
+ * A setup is sound when G1[i] = [tau^i] P0 and G2[j] = [tau^j] Q0 for one tau that nobody
+ * knows.  kzgx_srs_check tests each point on its own (canonical, on the curve, in the
+ * subgroup); a file of valid subgroup points that are not consecutive powers passes it.
+ * The entries here are one step of a powers-of-tau ceremony (DESIGN.md "Setup ceremony"):
+ * re-randomise tau with a fresh secret, test that a setup has the structure above, and test
+ * one contribution against its predecessor.  No transcript format, no verifier of a chain
+ * of contributions and no hashing of s: callers compose those from these three. */
+/* G1[i] <- [s^(g1_start+i)] G1[i], G2[j] <- [s^(g2_start+j)] G2[j] for every installed
+ * point, one lane per point on the device (a 256-bit double-and-add over the lane's own
+ * point; the two halves run side by side on two streams): a setup for tau becomes a setup
+ * for tau s.  Infinite entries stay infinite.
+ *  s: canonical, 4 uint64.  s = 0 or s >= r: KZGX_ERR_ARG, before any device work (the
+ *   setup is unchanged).  No G1 SRS: KZGX_ERR_NO_SRS.
+ *  g1_start / g2_start: the power of the first installed point, as kzgx_gen_srs_g1's
+ *   start (a sharded context that holds powers start.. passes the same start).
+ *  The G2 half is updated iff one is installed; both halves are computed into fresh buffers
+ *   and installed together, so a failure leaves the old setup, never half of each.
+ *  witness_g2_xy (8 / 12 uint64, may be NULL): [s] times the curve's G2 generator, what
+ *   kzgx_srs_verify_update needs beside the old and the new G1[1].
+ *  Afterwards the context is as after kzgx_load_srs_g1 + kzgx_load_srs_g2 of the new
+ *   points: every derived table (the MSM tables, the G2 window table, the verify tables)
+ *   and every cached all-domain / coset setup is rebuilt from them, on the call or on first
+ *   use.  A default table shared with other contexts is released, not written: the other
+ *   contexts keep the table of the old setup.
+ *  The call zeroes its device copy of s before it returns; the caller's copy is the
+ *   caller's to forget. */
+int kzgx_srs_update(kzgx_ctx* ctx, const uint64_t* s, size_t g1_start, size_t g2_start, uint64_t* witness_g2_xy);
+/* Is the installed setup (P_0..P_(n-1); Q_0..Q_(m-1)) a run of consecutive powers of one tau?
+ *  A  = sum_{i<n-1} rho^i P_i      B  = sum_{i<n-1} rho^i P_(i+1)     one batch of two G1 MSMs
+ *  A2 = sum_{j<m-1} sigma^j Q_j    B2 = sum_{j<m-1} sigma^j Q_(j+1)   the G2 MSM, twice
+ *  *g1_ok = [e(B, Q_0) == e(A, Q_1)] and P_0 != O and (n < 2 or P_1 != O)
+ *  *g2_ok = [e(P_1, A2) == e(P_0, B2)] and Q_0 != O
+ * and, with KZGX_SRS_STRUCT_GENERATORS in flags, both also require P_0 and Q_0 to be the
+ * curve's generators (what kzgx_gen_srs_g1 / kzgx_gen_srs_g2 start from).  The powers of the
+ * challenges are built on the device (one launch per challenge, each lane its own power).
+ *  rho, sigma: canonical scalars, 4 uint64 each.  Explicit values make the answer exactly
+ *   the equations above and nothing else: errors that cancel under that rho pass.  NULL
+ *   draws a 128-bit value from std::random_device, as kzgx_verify_aggregate does (the
+ *   bound below then reads (n - 2) / 2^128).
+ *  Two conditions, as for the aggregate:
+ *   - the pairing is bilinear only on the order-r subgroups, so the test means something
+ *     only for members: run kzgx_srs_check with subgroup = 1 first;
+ *   - for members, a setup that is not consecutive powers passes with probability at most
+ *     (n - 2) / r over a uniform rho ((m - 2) / r over sigma): a nonzero polynomial of that
+ *     degree in the challenge vanishes.
+ *  n = 1: *g1_ok comes from the non-degeneracy test alone, and *g2_ok = 0 (its equation
+ *   needs P_1).  No G1 SRS, or fewer than 2 G2 points: KZGX_ERR_NO_SRS.  rho or sigma >= r,
+ *   unknown flag bits: KZGX_ERR_ARG. */
+int kzgx_srs_verify_structure(kzgx_ctx* ctx, const uint64_t* rho, const uint64_t* sigma, int flags, int* g1_ok,
+                              int* g2_ok);
+#define KZGX_SRS_STRUCT_GENERATORS 1 /* also require G1[0], G2[0] == the curve's generators */
+/* One contribution against its predecessor: prev and new are G1[1] ([tau]G1) before and
+ * after, W the contributor's witness [s]G2gen.
+ *  *ok = [e(new, G2gen) == e(prev, W)] and W != O and new != O
+ * (all-zero = O), two pairings in one batch.  Needs no SRS.  NULL arguments: KZGX_ERR_ARG.
+ * As above, meaningful only for subgroup members (kzgx_g1_check_batch, kzgx_g2_check_batch). */
+int kzgx_srs_verify_update(kzgx_ctx* ctx, const uint64_t* prev_tau_g1_xy, const uint64_t* new_tau_g1_xy,
+                           const uint64_t* witness_g2_xy, int* ok);
+
 #ifdef __cplusplus
 }
 #endif

@@ -927,6 +927,34 @@ bool trusted_setup::check_setup(bool subgroup) {
   return g1_ok != 0 && g2_ok != 0;
 }
 
+G2 trusted_setup::contribute(const Fr& s) {
+  const int nl = base_limbs();
+  std::vector<uint64_t> w(4 * nl, 0);
+  check(kzgx_srs_update(ctx, s.v.data(), 0, 0, w.data()), "kzgx_srs_update");
+  return to_g2(w.data(), false);  // s != 0: the witness is finite
+}
+
+bool trusted_setup::verify_structure(bool generators) {
+  int g1_ok = 0, g2_ok = 0;
+  check(kzgx_srs_verify_structure(ctx, nullptr, nullptr, generators ? KZGX_SRS_STRUCT_GENERATORS : 0, &g1_ok, &g2_ok),
+        "kzgx_srs_verify_structure");
+  return g1_ok != 0 && g2_ok != 0;
+}
+
+bool trusted_setup::verify_contribution(const G1& prev_tau, const G1& new_tau, const G2& witness) {
+  const int nl = base_limbs();
+  std::vector<uint64_t> p(2 * nl, 0), q(2 * nl, 0), w(4 * nl, 0);  // infinity = all zero
+  for (int i = 0; i < nl; i++) {
+    if (!prev_tau.inf) p[i] = prev_tau.x[i], p[nl + i] = prev_tau.y[i];
+    if (!new_tau.inf) q[i] = new_tau.x[i], q[nl + i] = new_tau.y[i];
+    if (!witness.inf)
+      w[i] = witness.x0[i], w[nl + i] = witness.x1[i], w[2 * nl + i] = witness.y0[i], w[3 * nl + i] = witness.y1[i];
+  }
+  int ok = 0;
+  check(kzgx_srs_verify_update(default_ctx(), p.data(), q.data(), w.data(), &ok), "kzgx_srs_verify_update");
+  return ok != 0;
+}
+
 bool trusted_setup::aggregated(std::vector<commit>& commits, std::vector<proof>& proofs,
                                const std::vector<std::pair<Fr, Fr>>& points, bool checked, bool check_subgroup) {
   const size_t m = commits.size();

@@ -542,7 +542,7 @@ int kzgx_init_device(int curve, int device) {
       kzgx::warm_srs,        kzgx::warm_pairing,    kzgx::warm_verify_wave, kzgx::warm_latency,
       kzgx::warm_fixed_bn_a, kzgx::warm_fixed_bn_b, kzgx::warm_fixed_bn_c,  kzgx::warm_fixed_bn_d,
       kzgx::warm_fixed_bls_a, kzgx::warm_fixed_bls_b, kzgx::warm_fixed_bls_c, kzgx::warm_fixed_bls_d,
-      kzgx::warm_subgroup,   kzgx::warm_msm_joint,  kzgx::warm_joint_horner};
+      kzgx::warm_subgroup,   kzgx::warm_msm_joint,  kzgx::warm_joint_horner, kzgx::warm_srs_update};
   for (auto f : warm) KZGX_TRY(f(st));
   // the generator comb tables (per process, per device and curve)
   kzgx::GenTables g;
@@ -3456,6 +3456,198 @@ int kzgx_verify_blobs_batch(kzgx_ctx* ctx, const void* blobs, unsigned log2n, si
 int kzgx_verify_blobs_each(kzgx_ctx* ctx, const void* blobs, unsigned log2n, size_t count, int flags,
                            const uint8_t* commit_records, const uint8_t* proof_records, int subgroup, int* ok) {
   return blob_verify_host(ctx, blobs, log2n, count, flags, commit_records, proof_records, nullptr, subgroup, true, ok);
+}
+
+}  // extern "C"
+
+/* ---- setup ceremony -------------------------------------------------------------- */
+namespace {
+// v < r for a canonical 4 x 64-bit scalar; zero passes only with allow_zero
+bool fr_in_range(int curve, const uint64_t* v, bool allow_zero) {
+  const uint32_t* p = curve == KZGX_CURVE_BN254 ? kzgx::BN254Fr::P : kzgx::BLS12381Fr::P;
+  if ((v[0] | v[1] | v[2] | v[3]) == 0) return allow_zero;
+  for (int i = 3; i >= 0; i--) {
+    const uint64_t r = (uint64_t)p[2 * i] | ((uint64_t)p[2 * i + 1] << 32);
+    if (v[i] != r) return v[i] < r;
+  }
+  return false;  // v == r
+}
+
+bool all_zero(const uint8_t* p, size_t bytes) {
+  return std::all_of(p, p + bytes, [](uint8_t b) { return b == 0; });
+}
+}  // namespace
+
+extern "C" {
+
+int kzgx_srs_update(kzgx_ctx* ctx, const uint64_t* s, size_t g1_start, size_t g2_start, uint64_t* witness_g2_xy) {
+  KZGX_TRY(activate(ctx));
+  if (!s || !fr_in_range(ctx->c.curve, s, false)) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  const size_t n = ctx->c.n_srs, m = ctx->n_srs2;
+  if (n > 0x7fffffffu || m > 0x7fffffffu) return KZGX_ERR_ARG;
+  hipStream_t st = ctx->c.stream;
+  const int curve = ctx->c.curve;
+  const size_t p1 = point_words(ctx) * 4, p2 = 2 * p1;
+  // one staging block: s | witness
+  void* d_blk;
+  KZGX_TRY(stage(ctx, 0, 32 + p2, &d_blk));
+  uint32_t* d_s = (uint32_t*)d_blk;
+  uint32_t* d_wit = d_s + 8;
+  // both halves go into fresh buffers and are installed together below: a
+  // failure up to there leaves the old setup whole
+  struct Fresh {
+    uint32_t *g1 = nullptr, *g2 = nullptr;
+    ~Fresh() {
+      if (g1) (void)hipFree(g1);
+      if (g2) (void)hipFree(g2);
+    }
+  } fresh;
+  KZGX_TRY_HIP(hipMalloc((void**)&fresh.g1, n * p1));
+  if (m) KZGX_TRY_HIP(hipMalloc((void**)&fresh.g2, m * p2));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_s, s, 32, hipMemcpyHostToDevice, st));
+  // the G2 half (a few latency-bound waves; the witness [s] G2gen is one more
+  // lane of its launch) forks onto the side stream, as verify_proof's does,
+  // and runs beside the G1 half
+  KZGX_TRY(side_ready(ctx));
+  hipStream_t sd = ctx->side;
+  KZGX_TRY_HIP(hipEventRecord(ctx->ev_fork, st));
+  KZGX_TRY_HIP(hipStreamWaitEvent(sd, ctx->ev_fork, 0));
+  const int rg2 = kzgx::srs_update_g2(curve, d_s, g2_start, m, ctx->d_srs2_canon, fresh.g2,
+                                      witness_g2_xy ? d_wit : nullptr, sd);
+  // (joined before any return below: the side work reads s and writes the fresh buffers)
+  const hipError_t jr = hipEventRecord(ctx->ev_join, sd);
+  if (rg2 != KZGX_OK || jr != hipSuccess) {
+    (void)hipStreamSynchronize(sd);
+    return rg2 != KZGX_OK ? rg2 : kzgx::hip_fail(jr);
+  }
+  const int rg1 = kzgx::srs_update_g1(curve, d_s, g1_start, n, ctx->d_srs_canon, fresh.g1, st);
+  KZGX_TRY_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
+  if (rg1 != KZGX_OK) {
+    (void)hipStreamSynchronize(st);
+    return rg1;
+  }
+  if (witness_g2_xy) KZGX_TRY_HIP(hipMemcpyAsync(witness_g2_xy, d_wit, p2, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemsetAsync(d_s, 0, 32, st));  // the staged copy of the secret
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  // install, as kzgx_load_srs_g1 + kzgx_load_srs_g2 of the new points: every
+  // derived table and cached setup is stale.  srs_upload releases this
+  // context's reference to a shared default table and attaches to (or
+  // builds) the table of the new points; a table other contexts hold is
+  // never written.  hipFree waits for work that may still read the old points.
+  ctx->vw_ready = false;
+  cells_g2_drop(ctx);
+  kzgx::prove_all_drop(&ctx->c);
+  ctx->g2tab_n = 0;
+  std::swap(ctx->d_srs_canon, fresh.g1);
+  ctx->srs_canon_b = n * p1;
+  if (m) {
+    std::swap(ctx->d_srs2_canon, fresh.g2);
+    ctx->srs2_canon_b = m * p2;
+  }
+  KZGX_TRY(kzgx::srs_upload(&ctx->c, ctx->d_srs_canon, n));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  return setup_finish(ctx);
+}
+
+int kzgx_srs_verify_structure(kzgx_ctx* ctx, const uint64_t* rho, const uint64_t* sigma, int flags, int* g1_ok,
+                              int* g2_ok) {
+  KZGX_TRY(activate(ctx));
+  if (!g1_ok || !g2_ok || (flags & ~KZGX_SRS_STRUCT_GENERATORS)) return KZGX_ERR_ARG;
+  const int curve = ctx->c.curve;
+  if ((rho && !fr_in_range(curve, rho, true)) || (sigma && !fr_in_range(curve, sigma, true))) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0 || ctx->n_srs2 < 2) return KZGX_ERR_NO_SRS;
+  const size_t n = ctx->c.n_srs, m = ctx->n_srs2;
+  if (n > 0x7fffffffu || m > ((size_t)1 << 24)) return KZGX_ERR_ARG;  // (the G2 MSM's limit)
+  // library-drawn challenges: independent 128-bit values
+  uint64_t ch[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::random_device rd;
+  for (int k = 0; k < 2; k++) {
+    const uint64_t* given = k == 0 ? rho : sigma;
+    for (int j = 0; j < 4; j++) ch[4 * k + j] = given ? given[j] : j < 2 ? ((uint64_t)rd() << 32) | (uint64_t)rd() : 0;
+  }
+  hipStream_t st = ctx->c.stream;
+  const size_t p1 = point_words(ctx) * 4, p2 = 2 * p1, fb = 6 * p1;
+  // the scalar rows (stage 0; the G2 rows reuse the G1 rows' place) and one
+  // small block (stage 1):
+  //   rho | sigma | generators | G1: A, B, P_1, P_0 | G2: Q_1, Q_0, A2, B2 | infinity flags | 4 Fp12
+  const size_t o_gen = 64, o_g1 = o_gen + p1 + p2, o_g2 = o_g1 + 4 * p1, o_fl = o_g2 + 4 * p2, o_out = o_fl + 32,
+               blk_b = o_out + 4 * fb;
+  void *d_rows, *d_blk;
+  KZGX_TRY(stage(ctx, 0, std::max(n, m) * 64, &d_rows));
+  KZGX_TRY(stage(ctx, 1, blk_b, &d_blk));
+  char* blk = (char*)d_blk;
+  uint32_t* d_fl = (uint32_t*)(blk + o_fl);
+  KZGX_TRY_HIP(hipMemsetAsync(blk + o_g1, 0, o_out - o_g1, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(blk, ch, 64, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx::curve_generators(curve, (uint32_t*)(blk + o_gen), st));
+  // G1: A = sum rho^i P_i and B = sum rho^i P_(i+1), one batch of two MSMs over the installed SRS
+  if (n >= 2) {
+    uint32_t* row0 = (uint32_t*)d_rows;
+    KZGX_TRY(kzgx::fr_powers(curve, (const uint32_t*)blk, n - 1, row0, row0 + n * 8, st));
+    KZGX_TRY(kzgx_msm_g1_batch_device(ctx, row0, n, 2, n, blk + o_g1, d_fl, nullptr));
+    KZGX_TRY_HIP(hipMemcpyAsync(blk + o_g1 + 2 * p1, (const char*)ctx->d_srs_canon + p1, p1, hipMemcpyDeviceToDevice,
+                                st));
+  }
+  KZGX_TRY_HIP(hipMemcpyAsync(blk + o_g1 + 3 * p1, ctx->d_srs_canon, p1, hipMemcpyDeviceToDevice, st));
+  // G2: A2 = sum sigma^j Q_j and B2 = sum sigma^j Q_(j+1), the same two rows through the G2 MSM
+  {
+    uint32_t* row0 = (uint32_t*)d_rows;
+    KZGX_TRY(kzgx::fr_powers(curve, (const uint32_t*)(blk + 32), m - 1, row0, row0 + m * 8, st));
+    const uint32_t* tab = g2_table(ctx, m, st);
+    KZGX_TRY(kzgx::msm_g2(&ctx->c, row0, ctx->d_srs2_canon, m, (uint32_t*)(blk + o_g2 + 2 * p2), d_fl + 6, st, tab));
+    KZGX_TRY(kzgx::msm_g2(&ctx->c, row0 + m * 8, ctx->d_srs2_canon, m, (uint32_t*)(blk + o_g2 + 3 * p2), d_fl + 7, st,
+                          tab));
+    KZGX_TRY_HIP(hipMemcpyAsync(blk + o_g2, (const char*)ctx->d_srs2_canon + p2, p2, hipMemcpyDeviceToDevice, st));
+    KZGX_TRY_HIP(hipMemcpyAsync(blk + o_g2 + p2, ctx->d_srs2_canon, p2, hipMemcpyDeviceToDevice, st));
+  }
+  // e(A, Q_1), e(B, Q_0), e(P_1, A2), e(P_0, B2): the pairing value is unique, so words compare
+  KZGX_TRY(kzgx::pairing_batch(&ctx->c, (const uint32_t*)(blk + o_g1), d_fl, (const uint32_t*)(blk + o_g2), d_fl + 4, 4,
+                               (uint32_t*)(blk + o_out), st));
+  std::vector<uint8_t> h(blk_b);
+  KZGX_TRY_HIP(hipMemcpyAsync(h.data() + o_gen, blk + o_gen, blk_b - o_gen, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  const uint8_t *P1 = h.data() + o_g1 + 2 * p1, *P0 = h.data() + o_g1 + 3 * p1, *Q0 = h.data() + o_g2 + p2;
+  const uint8_t* out = h.data() + o_out;
+  bool ok1 = std::memcmp(out, out + fb, fb) == 0 && !all_zero(P0, p1) && (n < 2 || !all_zero(P1, p1));
+  // n = 1: there is no P_1 to test the G2 powers against
+  bool ok2 = n >= 2 && std::memcmp(out + 2 * fb, out + 3 * fb, fb) == 0 && !all_zero(Q0, p2);
+  if (flags & KZGX_SRS_STRUCT_GENERATORS) {
+    const bool gens = std::memcmp(P0, h.data() + o_gen, p1) == 0 && std::memcmp(Q0, h.data() + o_gen + p1, p2) == 0;
+    ok1 = ok1 && gens;
+    ok2 = ok2 && gens;
+  }
+  *g1_ok = ok1 ? 1 : 0;
+  *g2_ok = ok2 ? 1 : 0;
+  return KZGX_OK;
+}
+
+int kzgx_srs_verify_update(kzgx_ctx* ctx, const uint64_t* prev_tau_g1_xy, const uint64_t* new_tau_g1_xy,
+                           const uint64_t* witness_g2_xy, int* ok) {
+  KZGX_TRY(activate(ctx));
+  if (!prev_tau_g1_xy || !new_tau_g1_xy || !witness_g2_xy || !ok) return KZGX_ERR_ARG;
+  hipStream_t st = ctx->c.stream;
+  const size_t p1 = point_words(ctx) * 4, p2 = 2 * p1, fb = 6 * p1;
+  // generators (G1, then G2) | G1: new, prev | G2: G2gen, W | 2 Fp12
+  const size_t o_g1 = p1 + p2, o_g2 = o_g1 + 2 * p1, o_out = o_g2 + 2 * p2;
+  void* d_blk;
+  KZGX_TRY(stage(ctx, 1, o_out + 2 * fb, &d_blk));
+  char* blk = (char*)d_blk;
+  KZGX_TRY(kzgx::curve_generators(ctx->c.curve, (uint32_t*)blk, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(blk + o_g1, new_tau_g1_xy, p1, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(blk + o_g1 + p1, prev_tau_g1_xy, p1, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(blk + o_g2, blk + p1, p2, hipMemcpyDeviceToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(blk + o_g2 + p2, witness_g2_xy, p2, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx::pairing_batch(&ctx->c, (const uint32_t*)(blk + o_g1), nullptr, (const uint32_t*)(blk + o_g2), nullptr, 2,
+                               (uint32_t*)(blk + o_out), st));
+  std::vector<uint8_t> out(2 * fb);
+  KZGX_TRY_HIP(hipMemcpyAsync(out.data(), blk + o_out, 2 * fb, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  *ok = std::memcmp(out.data(), out.data() + fb, fb) == 0 && !all_zero((const uint8_t*)witness_g2_xy, p2) &&
+                !all_zero((const uint8_t*)new_tau_g1_xy, p1)
+            ? 1
+            : 0;
+  return KZGX_OK;
 }
 
 }  // extern "C"

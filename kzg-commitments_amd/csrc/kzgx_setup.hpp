@@ -25,6 +25,7 @@ int warm_latency(hipStream_t st);
 int warm_subgroup(hipStream_t st);
 int warm_msm_joint(hipStream_t st);
 int warm_joint_horner(hipStream_t st);
+int warm_srs_update(hipStream_t st);
 // the fixed-base MSM's per-window objects (msm_fixed_inst.hip, one per group)
 int warm_fixed_bn_a(hipStream_t st);
 int warm_fixed_bn_b(hipStream_t st);
@@ -56,6 +57,21 @@ int gen_srs_g1_comb(int curve, const uint32_t* d_tau, size_t start, size_t n, co
                     uint32_t* d_out, hipStream_t st);
 int gen_srs_g2_comb(int curve, const uint32_t* d_tau, size_t start, size_t n, const uint32_t* g2_comb,
                     uint32_t* d_out, hipStream_t st);
+
+// The setup ceremony's kernels (srs_update.hip).  One contribution:
+// out[i] = [s^(start + i)] in[i] over n canonical affine G1 / G2 points, a
+// lane per point (in == out allowed; all-zero = infinity stays all-zero).
+// d_witness (G2 only, may be null): one more lane writes [s] G2gen there
+int srs_update_g1(int curve, const uint32_t* d_s, size_t start, size_t n, const uint32_t* d_in, uint32_t* d_out,
+                  hipStream_t st);
+int srs_update_g2(int curve, const uint32_t* d_s, size_t start, size_t n, const uint32_t* d_in, uint32_t* d_out,
+                  uint32_t* d_witness, hipStream_t st);
+// the curve's generators, canonical affine: the G1 point, then the G2 point
+int curve_generators(int curve, uint32_t* d_out, hipStream_t st);
+// row0[i] = rho^i, i < count (canonical, 8 words each).  With row1, the two
+// rows of the structure test, count + 1 scalars each: row0 = (1, rho, ..,
+// rho^(count-1), 0) and row1 = (0, 1, rho, .., rho^(count-1))
+int fr_powers(int curve, const uint32_t* d_rho, size_t count, uint32_t* d_row0, uint32_t* d_row1, hipStream_t st);
 
 // The odd multiples (2 j + 1) B[w][i], j < H, of every window base into the
 // fixed-base table at strides (is, ws) words, by batch-affine chains: each

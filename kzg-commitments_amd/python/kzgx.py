@@ -55,6 +55,7 @@ EXPORTS = [
     "kzgx_evals_at_batch", "kzgx_evals_at_batch_device", "kzgx_prove_blobs_batch", "kzgx_prove_blobs_batch_device",
     "kzgx_verify_blobs_batch", "kzgx_verify_blobs_batch_device", "kzgx_verify_blobs_each",
     "kzgx_verify_blobs_each_device",
+    "kzgx_srs_update", "kzgx_srs_verify_structure", "kzgx_srs_verify_update",
 ]
 
 
@@ -86,6 +87,8 @@ ENC_SEC1 = _header_define("KZGX_ENC_SEC1")
 # blob proofs: elements are 32-byte big-endian (checked < r), and the scalars per internal chunk of blobs
 BLOB_BYTES = _header_define("KZGX_BLOB_BYTES")
 BLOB_CHUNK_SCALARS = _header_define("KZGX_BLOB_CHUNK_SCALARS")
+# setup ceremony: the structure test also requires G1[0], G2[0] to be the curve's generators
+SRS_STRUCT_GENERATORS = _header_define("KZGX_SRS_STRUCT_GENERATORS")
 
 _lib = None
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -283,6 +286,9 @@ def lib():
                                                       intp]),
             "kzgx_verify_blobs_each_device": (ctypes.c_int, [vp, vp, ctypes.c_uint, sz, ctypes.c_int, vp, vp,
                                                              ctypes.c_int, vp, vp]),
+            "kzgx_srs_update": (ctypes.c_int, [vp, u64p, sz, sz, u64p]),
+            "kzgx_srs_verify_structure": (ctypes.c_int, [vp, u64p, u64p, ctypes.c_int, intp, intp]),
+            "kzgx_srs_verify_update": (ctypes.c_int, [vp, u64p, u64p, u64p, intp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -903,6 +909,34 @@ class Context:
         a, b = ctypes.c_int(0), ctypes.c_int(0)
         _chk(lib().kzgx_srs_check(self.h, int(bool(subgroup)), ctypes.byref(a), ctypes.byref(b)), "kzgx_srs_check")
         return bool(a.value), bool(b.value)
+
+    # ---- setup ceremony ----
+    def srs_update(self, s: int, g1_start: int = 0, g2_start: int = 0, witness: bool = True):
+        """kzgx_srs_update: G1[i] <- [s^(g1_start+i)] G1[i], G2[j] <- [s^(g2_start+j)] G2[j] on the device,
+        then the install path of a loaded setup; -> the witness [s]G2gen (4 * W64 words), or None."""
+        t = np.array([(s >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+        w = np.zeros(4 * self.w64, dtype=np.uint64) if witness else None
+        _chk(lib().kzgx_srs_update(self.h, _p(t), g1_start, g2_start, _p(w)), "kzgx_srs_update")
+        return w
+
+    def srs_verify_structure(self, rho: int | None = None, sigma: int | None = None, generators: bool = False):
+        """kzgx_srs_verify_structure: (g1_ok, g2_ok), the installed points are consecutive powers of one
+        tau; rho / sigma None = drawn by the library, explicit = exactly the documented equations."""
+        ch = [None if v is None else np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)],
+                                              dtype=np.uint64) for v in (rho, sigma)]
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _chk(lib().kzgx_srs_verify_structure(self.h, _p(ch[0]), _p(ch[1]), SRS_STRUCT_GENERATORS if generators else 0,
+                                             ctypes.byref(a), ctypes.byref(b)), "kzgx_srs_verify_structure")
+        return bool(a.value), bool(b.value)
+
+    def srs_verify_update(self, prev_tau_g1, new_tau_g1, witness_g2) -> bool:
+        """kzgx_srs_verify_update: e(new, G2gen) == e(prev, W), W and new finite (all-zero = infinity)."""
+        p = np.ascontiguousarray(prev_tau_g1, dtype=np.uint64).reshape(2 * self.w64)
+        q = np.ascontiguousarray(new_tau_g1, dtype=np.uint64).reshape(2 * self.w64)
+        w = np.ascontiguousarray(witness_g2, dtype=np.uint64).reshape(4 * self.w64)
+        ok = ctypes.c_int(0)
+        _chk(lib().kzgx_srs_verify_update(self.h, _p(p), _p(q), _p(w), ctypes.byref(ok)), "kzgx_srs_verify_update")
+        return bool(ok.value)
 
     def verify_aggregate_checked(self, commits, proofs, zs, ys, challenges=None, commit_inf=None, proof_inf=None,
                                  subgroup: bool = True) -> bool:

@@ -73,6 +73,110 @@ BLS_X2 = X * X  # the subgroup test's exponent: [x^2]P = (beta x, -y)
 assert (BLS_X2 * BLS_X2 - BLS_X2 + 1) == BLS_R
 
 # --------------------------------------------------------------------------
+# Endomorphism split of the block-table MSM (msm_joint.hip, GLV).  Both curves
+# have j = 0: phi(x, y) = (beta x, y) = [lambda]P on the order-r subgroup,
+# beta^3 = 1 in Fp, lambda^3 = 1 mod r.  A scalar k < r is written
+# k = k1 + lambda k2 (mod r) with both halves odd and |k1|, |k2| < 2^128:
+#   * (v1, v2) = ((a1, b1), (a2, b2)) is the Euclid short basis of the lattice
+#     {(a, b): a + b lambda = 0 mod r}, signs chosen so that the coordinates of
+#     (k, 0) in it, x1 = k n1 / r and x2 = k n2 / r with n1 = |b2|, n2 = |b1|,
+#     are not negative;
+#   * f_i = floor(k g_i / 2^SHIFT), g_i = floor(2^SHIFT n_i / r): f_i <= x_i <
+#     f_i + 1 + 2^(255 - SHIFT) for k < r < 2^255;
+#   * c_i is the one of f_i, f_i + 1 whose parity makes both halves odd:
+#     c1 = b2 (k + 1) + a2, c2 = b1 (k + 1) + a1 (mod 2), the inverse of the
+#     basis mod 2 (its determinant +-r is odd) applied to (k + 1, 1);
+#   * (k1, k2) = (k, 0) - c1 v1 - c2 v2 = e1 v1 + e2 v2 with |e_i| < 1 + 2^(255 -
+#     SHIFT), so |k1| < (1 + 2^(255 - SHIFT)) (|a1| + |a2|) and likewise k2 with
+#     the b's: asserted below to be at most 2^128.
+# The device computes both halves mod 2^160 in two's complement: NEG[j] = the
+# words of -a1, -a2, -b1, -b2 mod 2^160.
+# --------------------------------------------------------------------------
+GLV_SHIFT = 288
+
+
+def _cube_roots(m):
+    g = 2
+    while pow(g, (m - 1) // 3, m) == 1:
+        g += 1
+    w = pow(g, (m - 1) // 3, m)
+    return w, w * w % m
+
+
+def glv_data(name):
+    if name == "BN254":
+        p, r, G = BN_P, BN_R, (BN_P - 1, 1)
+        beta = min(_cube_roots(p))
+        lams = [l for l in _cube_roots(r) if _g1_smul(p, G, l) == (beta * G[0] % p, G[1])]
+        assert len(lams) == 1
+        lam = lams[0]
+    else:  # the subgroup test's beta: lambda = -x^2
+        p, r, G = BLS_P, BLS_R, (BLS_GX, BLS_GY)
+        beta, lam = BLS_BETA, (-BLS_X2) % BLS_R
+        assert _g1_smul(p, G, lam) == (beta * G[0] % p, G[1])
+    assert (lam * lam + lam + 1) % r == 0 and pow(beta, 3, p) == 1 and beta != 1
+    # Euclid on (r, lambda): every remainder row (s, t) has s + (-t) lambda = 0 mod r
+    rows = [(r, 0), (lam, 1)]
+    while rows[-1][0] * rows[-1][0] >= r:
+        q = rows[-2][0] // rows[-1][0]
+        rows.append((rows[-2][0] - q * rows[-1][0], rows[-2][1] - q * rows[-1][1]))
+    v1 = (rows[-1][0], -rows[-1][1])
+    cand = [(rows[-2][0], -rows[-2][1])]
+    q = rows[-2][0] // rows[-1][0]
+    cand.append((rows[-2][0] - q * rows[-1][0], -(rows[-2][1] - q * rows[-1][1])))
+    v2 = min(cand, key=lambda v: max(abs(v[0]), abs(v[1])))
+    (a1, b1), (a2, b2) = v1, v2
+    det = a1 * b2 - a2 * b1
+    assert abs(det) == r
+    if b2 * det < 0:  # x1 = k b2 / det
+        a1, b1, det = -a1, -b1, -det
+    if -b1 * det < 0:  # x2 = -k b1 / det
+        a2, b2, det = -a2, -b2, -det
+    assert b2 * det >= 0 and -b1 * det >= 0
+    for a, b in ((a1, b1), (a2, b2)):
+        assert (a + b * lam) % r == 0
+    n1, n2 = abs(b2), abs(b1)
+    g1, g2 = (n1 << GLV_SHIFT) // r, (n2 << GLV_SHIFT) // r
+    assert r < 1 << 255 and max(g1, g2) < 1 << 192
+    # |k_i| < (1 + 2^(255 - SHIFT)) (sum of the basis' entries in that coordinate) <= 2^128
+    for s in (abs(a1) + abs(a2), abs(b1) + abs(b2)):
+        assert s * ((1 << (GLV_SHIFT - 255)) + 1) <= 1 << (128 + GLV_SHIFT - 255)
+    par = (b2 & 1) | ((a2 & 1) << 1) | ((b1 & 1) << 2) | ((a1 & 1) << 3)
+    return dict(p=p, r=r, beta=beta, lam=lam, basis=((a1, b1), (a2, b2)), g=(g1, g2), par=par)
+
+
+def glv_split(name, k, d=None):
+    """the device's decomposition of k < r: (k1, k2), both odd, k1 + lambda k2 = k mod r"""
+    d = d or glv_data(name)
+    (a1, b1), (a2, b2) = d["basis"]
+    c1, c2 = (k * d["g"][0]) >> GLV_SHIFT, (k * d["g"][1]) >> GLV_SHIFT
+    c1 += (c1 ^ (b2 * (k + 1) + a2)) & 1
+    c2 += (c2 ^ (b1 * (k + 1) + a1)) & 1
+    return k - c1 * a1 - c2 * a2, -c1 * b1 - c2 * b2
+
+
+def glv_struct(name, L):
+    d = glv_data(name)
+    (a1, b1), (a2, b2) = d["basis"]
+    for k in (0, 1, 2, d["r"] - 1, d["lam"], d["r"] // 2):
+        k1, k2 = glv_split(name, k, d)
+        assert (k1 + d["lam"] * k2 - k) % d["r"] == 0 and k1 & 1 and k2 & 1 and max(abs(k1), abs(k2)) < 1 << 128
+    neg = ", ".join(arr((-v) % (1 << 160), 5) for v in (a1, a2, b1, b2))
+    return "\n".join([
+        "// endomorphism split (msm_joint.hip): phi(x, y) = (BETA x, y) = [LAMBDA]P; k = k1 + LAMBDA k2 mod r",
+        "struct %sGlv {" % name,
+        "  static constexpr uint32_t BETA29[%d] = %s;  // radix-2^29 Montgomery" % (L, arr29(mont29(d["beta"], d["p"], L), L)),
+        "  static constexpr uint32_t LAMBDA[8] = %s;  // canonical" % arr(d["lam"], 8),
+        "  static constexpr int SHIFT = %d;  // f_i = floor(k G[i] / 2^SHIFT)" % GLV_SHIFT,
+        "  static constexpr uint32_t G[2][6] = {%s, %s};  // floor(2^SHIFT |b2| / r), floor(2^SHIFT |b1| / r)" % (
+            arr(d["g"][0], 6), arr(d["g"][1], 6)),
+        "  static constexpr uint32_t NEG[4][5] = {%s};  // -a1, -a2, -b1, -b2 mod 2^160" % neg,
+        "  static constexpr uint32_t PAR = %du;  // parities: bit 0 b2, bit 1 a2, bit 2 b1, bit 3 a1" % d["par"],
+        "};",
+    ])
+
+
+# --------------------------------------------------------------------------
 # Compressed points (codec.hip).  Both primes are 3 mod 4, so a square a of Fp
 # has the root a^((p + 1) / 4); a is a square iff that power squares back to a.
 # In Fp2 = Fp[i] (p = 3 mod 4, complex method): a1 = a^((p - 3) / 4),
@@ -409,7 +513,10 @@ def main():
         # (poly.hip fe_inv_wave, the interpolation weights)
         field29("BN254Fr29", BN_R, 9),
         field29("BLS12381Fr29", BLS_R, 9),
+        glv_struct("BN254", 9),
+        glv_struct("BLS12381", 14),
         "struct BN254G1 {",
+        "  using Glv = BN254Glv;",
         "  using Fp = BN254Fp;",
         "  using Fp29 = BN254Fp29;",
         "  using Fr = BN254Fr;",
@@ -425,6 +532,7 @@ def main():
         *sqrt_consts(BN_P, 8),
         "};",
         "struct BLS12381G1 {",
+        "  using Glv = BLS12381Glv;",
         "  using Fp = BLS12381Fp;",
         "  using Fp29 = BLS12381Fp29;",
         "  using Fr = BLS12381Fr;",

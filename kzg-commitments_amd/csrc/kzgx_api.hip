@@ -575,6 +575,12 @@ int kzgx_create(kzgx_ctx** out, int curve, int device) {
     const int g = atoi(e);
     if (g == -1 || g == 0 || (g >= 2 && g <= 25)) ctx->c.fixed.joint.g_req = g;
   }
+  // the block table's endomorphism split: the curve's default unless set (1 on, 0 the 254 / 255-plane path)
+  ctx->c.fixed.joint.glv = kzgx::joint_glv_default(curve);
+  if (const char* e = getenv("KZGX_FIXED_JOINT_GLV")) {
+    if (e[0] == '0' && !e[1]) ctx->c.fixed.joint.glv = false;
+    if (e[0] == '1' && !e[1]) ctx->c.fixed.joint.glv = true;
+  }
   if (const char* e = getenv("KZGX_FIXED_JOINT_RANGES")) {  // kzgx_set_fixed_joint_ranges' default, for A/B runs
     const int r = atoi(e);
     if (r >= 0 && r <= 8) ctx->c.fixed.joint.ranges = (uint32_t)r;
@@ -3764,6 +3770,14 @@ int prim_selftest(int curve, int op, int mode, const uint32_t* in, size_t count,
 extern "C" int kzgx_debug_prim(kzgx_ctx* ctx, int op, int mode, const uint32_t* in, size_t count, uint32_t* out) {
   KZGX_TRY(activate(ctx));
   return kzgx::prim_selftest(ctx->c.curve, op, mode, in, count, out, ctx->c.stream);
+}
+
+// debug: the block table's endomorphism split of `count` scalars (8 words
+// each, any 256-bit value) as the index pass forms it, 9 words per scalar to
+// `out`: |k1| (4 words), |k2| (4 words), sign bits (bit 0: k1 < 0, bit 1: k2 < 0)
+extern "C" int kzgx_debug_joint_glv(kzgx_ctx* ctx, const uint32_t* scalars, size_t count, uint32_t* out) {
+  KZGX_TRY(activate(ctx));
+  return kzgx::joint_glv_debug(&ctx->c, scalars, count, out);
 }
 
 extern "C" int kzgx_debug_vw_bench(kzgx_ctx* ctx, int op, unsigned iters, double* res) {

@@ -132,6 +132,7 @@ struct FkSetup {
 struct JointTable {
   int g_req = 0;        // -1 automatic, 0 off, 2..25 forced (kzgx_set_fixed_joint)
   uint32_t ranges = 0;  // block ranges per MSM of the accumulation, 0 = automatic
+  bool glv = false;     // split every scalar with the curve endomorphism: 2 x 128 planes (KZGX_FIXED_JOINT_GLV)
   int g = 0;            // built table
   uint32_t blocks = 0;
   size_t n_t = 0;
@@ -376,6 +377,8 @@ int joint_msm(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n, siz
 // JOINT_NSEG R cooperative additions among them.  Measured per 2048-MSM BN254
 // launch, stage 1 + stage 2: 4 planes 0.147 + 0.856 ms, 8 planes 0.216 +
 // 0.729 ms, 16 planes 0.261 + 0.649 ms (profiles/joint_horner_serial_kernel_stats_seg*.csv).
+// With the endomorphism split (two chains of 127 doublings, stage 1 inlined):
+// 8 planes 0.156 + 0.351 ms, 16 planes 0.187 + 0.324 ms (profiles/joint_glv_*.csv).
 constexpr uint32_t JOINT_PL = 256;
 constexpr uint32_t JOINT_SEG = 16;
 constexpr uint32_t JOINT_NSEG = JOINT_PL / JOINT_SEG;
@@ -384,6 +387,16 @@ static_assert(JOINT_NSEG * JOINT_SEG == JOINT_PL, "whole segments");
 template <class C>
 int joint_horner_launch(const uint32_t* part, uint32_t batch, uint32_t R, uint32_t* segs, uint32_t* sums,
                         hipStream_t st);
+// the endomorphism split's pass: planes [0, 128) and [128, 256) are the two
+// halves' own sums S_1, S_2 (all JOINT_PL planes live); sums: 2 batch records;
+// out = S_1 + phi(S_2), canonical affine and infinity flags as k_fixed_finish's
+template <class C>
+int joint_horner_glv_launch(const uint32_t* part, uint32_t batch, uint32_t R, uint32_t* segs, uint32_t* sums,
+                            uint32_t* out, uint32_t* out_inf, hipStream_t st);
+// the split's default for a curve, and the split of count host scalars as the
+// index pass forms it (9 words each: |k1|, |k2|, sign bits) to host out
+bool joint_glv_default(int curve);
+int joint_glv_debug(Ctx* ctx, const uint32_t* scalars, size_t count, uint32_t* out);
 int srs_upload(Ctx* ctx, const uint32_t* d_canon, size_t n);
 // mixed additions / s of the fixed-base accumulation loop on L1-resident operands (msm_fixed.hip)
 int microbench_mixed_add(Ctx* ctx, double* rate);

@@ -26,10 +26,17 @@
 // ceil(n / g) bits(r) mixed additions per MSM: 164 x 254 = 41 656 at g = 25
 // over 4097 BN254 points against the c = 17 window table's 61 455.
 //
+// With the endomorphism split (JointTable::glv, KZGX_FIXED_JOINT_GLV; see
+// k_joint_index) the same table serves two 128-plane sums per MSM, S_1 and
+// S_2 with MSM = S_1 + phi(S_2): ceil(n / g) x 256 mixed additions (against
+// 254 / 255) and two Horner chains of 127 doublings side by side, not one of
+// 253 / 254.
+//
 // Passes of one call (profiler scopes):
 //   k_joint_index   (msm_scatter)  one 32-bit word per (block, plane)
 //   k_joint_accum   (msm_accum)    lane (MSM, plane) sums its plane's entries
-//   k_joint_horner1/2 (joint_horner.hip) + k_fixed_finish (msm_reduce)
+//   k_joint_horner1/2 (joint_horner.hip) + k_fixed_finish (msm_reduce);
+//   split: k_joint_horner1, k_joint_horner2_glv, k_joint_finish_glv
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -352,7 +359,87 @@ int joint_plan(int curve, int c, size_t n, int g_req, int* g, int* c_win) {
 // word is normalised to the stored half -- a top point's bit of 0 complements
 // it and sets JOINT_NEG -- and masked to g_b - 1 bits: idx < 2^(g_b - 1),
 // whatever the scalars.  Layout idx[b][block][plane], plane fastest.
+//
+// GLV (the endomorphism split, gen_consts.py "Endomorphism split"): the scalar
+// is written k = k1 + lambda k2 mod r with both halves odd and below 2^128 in
+// magnitude, and each half is recoded as above at 128 planes: u = |k_i| >> 1,
+// top digit +1, every sign flipped for a negative half.  Planes 0..127 are
+// half 0's (k1), 128..255 half 1's (k2): the MSM is S_1 + phi(S_2), each S
+// the half's own block-table sum.  Odd halves need no "even k runs as r - k" step; scalar 0
+// (and the padding lanes) splits like any other, into an odd pair that sums
+// to 0 mod r.
+template <int NA, int NB, int NO>
+KZGX_DEV void glv_mul_add(const uint32_t (&a)[NA], const uint32_t (&b)[NB], uint32_t (&acc)[NO]) {
+  // acc += a b mod 2^(32 NO)
+#pragma unroll
+  for (int i = 0; i < NA; i++) {
+    uint64_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      if (i + j < NO) {
+        const uint64_t v = (uint64_t)a[i] * b[j] + acc[i + j] + carry;
+        acc[i + j] = (uint32_t)v;
+        carry = v >> 32;
+      }
+    }
+#pragma unroll
+    for (int t = i + NB; t < NO; t++) {
+      const uint64_t v = (uint64_t)acc[t] + carry;
+      acc[t] = (uint32_t)v;
+      carry = v >> 32;
+    }
+  }
+}
+
+// canonical k < r -> h[0..3] = |k1|, h[4..7] = |k2| (both odd, < 2^128); bit i
+// of the return value: half i is negative
 template <class C>
+KZGX_DEV uint32_t glv_split(const uint32_t (&k)[8], uint32_t (&h)[8]) {
+  using G = typename C::Glv;
+  static_assert(G::SHIFT == 288, "f_i = words 9..13 of the 14-word product");
+  const uint32_t kp = (k[0] & 1u) ^ 1u;  // k + 1 mod 2
+  uint32_t c[2][5];
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    uint32_t t[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    glv_mul_add<8, 6, 14>(k, G::G[i], t);
+    // c_i = f_i or f_i + 1, whichever has the parity that makes both halves odd
+    const uint32_t PB = (G::PAR >> (2 * i)) & 1u, PA = (G::PAR >> (2 * i + 1)) & 1u;  // b2, a2 / b1, a1
+    const uint32_t want = (PB & kp) ^ PA;
+    uint64_t carry = (t[9] ^ want) & 1u;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+      const uint64_t v = (uint64_t)t[9 + j] + carry;
+      c[i][j] = (uint32_t)v;
+      carry = v >> 32;
+    }
+  }
+  uint32_t neg = 0;
+#pragma unroll
+  for (int half = 0; half < 2; half++) {
+    // k1 = k - c1 a1 - c2 a2, k2 = -c1 b1 - c2 b2, mod 2^160 (|k_i| < 2^128)
+    uint32_t v[5] = {0, 0, 0, 0, 0};
+    if (half == 0) {
+#pragma unroll
+      for (int j = 0; j < 5; j++) v[j] = k[j];
+    }
+    glv_mul_add<5, 5, 5>(c[0], G::NEG[2 * half], v);
+    glv_mul_add<5, 5, 5>(c[1], G::NEG[2 * half + 1], v);
+    const uint32_t sg = v[4] >> 31;
+    neg |= sg << half;
+    const uint32_t m = 0u - sg;  // |v| = (v ^ m) + sg
+    uint64_t carry = sg;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint64_t x = (uint64_t)(v[j] ^ m) + carry;
+      h[4 * half + j] = (uint32_t)x;
+      carry = x >> 32;
+    }
+  }
+  return neg;
+}
+
+template <class C, bool GLV>
 __global__ __launch_bounds__(64) void k_joint_index(const uint32_t* __restrict__ scalars, uint32_t n,
                                                     size_t stride_words, uint32_t n_t, uint32_t g, uint32_t nb,
                                                     uint32_t* __restrict__ idx) {
@@ -366,11 +453,24 @@ __global__ __launch_bounds__(64) void k_joint_index(const uint32_t* __restrict__
   uint32_t s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (li < gb && i < n) scalar_load(scalars + (size_t)b * stride_words + (size_t)i * 8, s);
   scalar_reduce<C>(s);
-  const uint32_t flip = odd_prepare<C>(s);    // s = u = k' >> 1 < 2^(BITS - 1); scalar 0 runs as r
-  s[(BITS - 1) >> 5] |= 1u << ((BITS - 1) & 31);  // d_{BITS-1} = +1
   const uint32_t keep = li < gb ? ~0u : 0u;   // lanes past the block offer 0 bits
+  if constexpr (GLV) {
+    uint32_t h[8];
+    const uint32_t neg = glv_split<C>(s, h);
 #pragma unroll
-  for (int k = 0; k < 8; k++) s[k] = (s[k] ^ (0u - flip)) & keep;
+    for (int half = 0; half < 2; half++) {
+      const uint32_t fl = 0u - ((neg >> half) & 1u);
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+        s[4 * half + k] = (__builtin_amdgcn_alignbit(h[4 * half + k + 1], h[4 * half + k], 1) ^ fl) & keep;
+      s[4 * half + 3] = (((h[4 * half + 3] >> 1) | 0x80000000u) ^ fl) & keep;  // u = |k_i| >> 1, d_127 = +1
+    }
+  } else {
+    const uint32_t flip = odd_prepare<C>(s);    // s = u = k' >> 1 < 2^(BITS - 1); scalar 0 runs as r
+    s[(BITS - 1) >> 5] |= 1u << ((BITS - 1) & 31);  // d_{BITS-1} = +1
+#pragma unroll
+    for (int k = 0; k < 8; k++) s[k] = (s[k] ^ (0u - flip)) & keep;
+  }
   const uint32_t low = gb ? (1u << (gb - 1)) - 1u : 0u;
   uint32_t* out = idx + ((size_t)b * nb + blk) * JOINT_PL + li;
 #pragma unroll
@@ -403,7 +503,7 @@ __global__ __launch_bounds__(64) void k_joint_index(const uint32_t* __restrict__
 // builder counted entries at infinity): the sum with such an entry, x = y =
 // 0, is dropped by per-limb selects, no branch; the kernel without it tests
 // nothing.
-template <class C, bool INF, int V = madd_variant<C>()>
+template <class C, bool INF, bool GLV = false, int V = madd_variant<C>()>
 __global__ __launch_bounds__(64, fixed_accum_waves<C>()) void k_joint_accum(
     const uint32_t* __restrict__ idx, uint32_t nb, uint32_t per, const uint32_t* __restrict__ tab, size_t bstride,
     uint32_t R, uint32_t* __restrict__ part) {
@@ -411,7 +511,9 @@ __global__ __launch_bounds__(64, fixed_accum_waves<C>()) void k_joint_accum(
   constexpr int PW = packed_words<C>();
   const uint32_t b = blockIdx.y, rho = blockIdx.x >> 2;
   const uint32_t w = (blockIdx.x & 3u) * 64 + threadIdx.x;
-  if (w >= (uint32_t)C::SCALAR_BITS) return;
+  if constexpr (!GLV) {  // the split's 2 x 128 planes are all live
+    if (w >= (uint32_t)C::SCALAR_BITS) return;
+  }
   const uint32_t b0 = rho * per, b1 = b0 + per < nb ? b0 + per : nb;
   Xyzz<C> acc = xyzz_inf<C>();
   if (b0 < b1) {
@@ -452,6 +554,12 @@ __global__ __launch_bounds__(64, fixed_accum_waves<C>()) void k_joint_accum(
 
 // The Horner pass over the partials (part[b][rho][plane]) is joint_horner.hip's.
 
+// The endomorphism split's default per curve (KZGX_FIXED_JOINT_GLV overrides
+// it at context creation): on for both, each measured faster in alternated
+// runs (BN254 cfg2 +3.0%, cfg3 +3.0%; BLS12-381 cfg4 +3.7%; DESIGN.md "Block
+// table").
+bool joint_glv_default(int curve) { return curve == KZGX_CURVE_BN254 || curve == KZGX_CURVE_BLS12381; }
+
 bool joint_serves(const FixedTable& ft, size_t n, size_t batch, bool xyzz_out) {
   const JointTable& jt = ft.joint;
   if (!jt.d || xyzz_out || n == 0 || n > jt.n_t) return false;
@@ -462,6 +570,7 @@ template <class C>
 static int joint_msm_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n, size_t batch,
                           size_t stride_words, uint32_t* d_out, uint32_t* d_out_inf, hipStream_t st) {
   const JointTable& jt = ft.joint;
+  const bool glv = jt.glv;
   constexpr size_t XB = xyzz_words<C>() * sizeof(uint32_t);
   static_assert(C::SCALAR_BITS <= (int)JOINT_PL && C::SCALAR_BITS > 192, "4 wavefronts of planes");
   const uint32_t nb = (uint32_t)((n + jt.g - 1) / jt.g);  // whole blocks beyond n sum to r (...) = O: skipped
@@ -478,17 +587,27 @@ static int joint_msm_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, s
   MsmWs& ws = *wsp;
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.jidx, batch * (size_t)nb * JOINT_PL * 4, &ws.jidx_b));
   KZGX_TRY(dev_alloc(ctx, (void**)&ws.fpart, batch * (size_t)R * JOINT_PL * XB, &ws.fpart_b));
-  // the Horner pass's segment sums [batch][R][JOINT_NSEG], then its [batch] results
-  KZGX_TRY(dev_alloc(ctx, (void**)&ws.fsum, batch * ((size_t)R * JOINT_NSEG + 1) * XB, &ws.fsum_b));
+  // the Horner pass's segment sums [batch][R][JOINT_NSEG], then its [batch] results (one per half under the split)
+  KZGX_TRY(dev_alloc(ctx, (void**)&ws.fsum, batch * ((size_t)R * JOINT_NSEG + 2) * XB, &ws.fsum_b));
   {
     ProfScope p(ctx, st, "msm_scatter");
-    hipLaunchKernelGGL(k_joint_index<C>, dim3((nb + 1) / 2, (unsigned)batch), dim3(64), 0, st, d_scalars, (uint32_t)n,
-                       stride_words, (uint32_t)jt.n_t, (uint32_t)jt.g, nb, ws.jidx);
+    if (glv)
+      hipLaunchKernelGGL((k_joint_index<C, true>), dim3((nb + 1) / 2, (unsigned)batch), dim3(64), 0, st, d_scalars,
+                         (uint32_t)n, stride_words, (uint32_t)jt.n_t, (uint32_t)jt.g, nb, ws.jidx);
+    else
+      hipLaunchKernelGGL((k_joint_index<C, false>), dim3((nb + 1) / 2, (unsigned)batch), dim3(64), 0, st, d_scalars,
+                         (uint32_t)n, stride_words, (uint32_t)jt.n_t, (uint32_t)jt.g, nb, ws.jidx);
   }
   {
     ProfScope p(ctx, st, "msm_accum");
     const size_t bstride = ((size_t)1 << (jt.g - 1)) * packed_words<C>();
-    if (jt.n_inf)
+    if (glv && jt.n_inf)
+      hipLaunchKernelGGL((k_joint_accum<C, true, true>), dim3(4 * R, (unsigned)batch), dim3(64), 0, st, ws.jidx, nb,
+                         per, jt.d, bstride, R, ws.fpart);
+    else if (glv)
+      hipLaunchKernelGGL((k_joint_accum<C, false, true>), dim3(4 * R, (unsigned)batch), dim3(64), 0, st, ws.jidx, nb,
+                         per, jt.d, bstride, R, ws.fpart);
+    else if (jt.n_inf)
       hipLaunchKernelGGL((k_joint_accum<C, true>), dim3(4 * R, (unsigned)batch), dim3(64), 0, st, ws.jidx, nb, per,
                          jt.d, bstride, R, ws.fpart);
     else
@@ -498,8 +617,12 @@ static int joint_msm_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, s
   {
     ProfScope p(ctx, st, "msm_reduce");
     uint32_t* sums = ws.fsum + batch * (size_t)R * JOINT_NSEG * xyzz_words<C>();
-    KZGX_TRY(joint_horner_launch<C>(ws.fpart, (uint32_t)batch, R, ws.fsum, sums, st));
-    fixed_finish_launch<C>(sums, (uint32_t)batch, d_out, d_out_inf, nullptr, st);
+    if (glv) {
+      KZGX_TRY(joint_horner_glv_launch<C>(ws.fpart, (uint32_t)batch, R, ws.fsum, sums, d_out, d_out_inf, st));
+    } else {
+      KZGX_TRY(joint_horner_launch<C>(ws.fpart, (uint32_t)batch, R, ws.fsum, sums, st));
+      fixed_finish_launch<C>(sums, (uint32_t)batch, d_out, d_out_inf, nullptr, st);
+    }
   }
   KZGX_TRY_HIP(hipGetLastError());
   return KZGX_OK;
@@ -510,6 +633,44 @@ int joint_msm(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, size_t n, siz
   return ctx->curve == KZGX_CURVE_BN254
              ? joint_msm_impl<BN254G1>(ctx, ft, d_scalars, n, batch, stride_words, d_out, d_out_inf, st)
              : joint_msm_impl<BLS12381G1>(ctx, ft, d_scalars, n, batch, stride_words, d_out, d_out_inf, st);
+}
+
+// debug: the split of count scalars as the index pass forms it; 9 words per
+// scalar: |k1| (4), |k2| (4), the sign bits
+template <class C>
+__global__ __launch_bounds__(64) void k_joint_glv_debug(const uint32_t* __restrict__ scalars, uint32_t count,
+                                                        uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  uint32_t s[8], h[8];
+  scalar_load(scalars + (size_t)i * 8, s);
+  scalar_reduce<C>(s);
+  const uint32_t neg = glv_split<C>(s, h);
+#pragma unroll
+  for (int k = 0; k < 8; k++) out[(size_t)i * 9 + k] = h[k];
+  out[(size_t)i * 9 + 8] = neg;
+}
+
+int joint_glv_debug(Ctx* ctx, const uint32_t* scalars, size_t count, uint32_t* out) {
+  if (!scalars || !out || count == 0 || count > (1u << 24)) return KZGX_ERR_ARG;
+  hipStream_t st = ctx->stream;
+  uint32_t *d_in = nullptr, *d_out = nullptr;
+  KZGX_TRY_HIP(hipMalloc((void**)&d_in, count * 32));
+  int rc = hipMalloc((void**)&d_out, count * 36) == hipSuccess ? KZGX_OK : KZGX_ERR_HIP;
+  if (rc == KZGX_OK && hipMemcpyAsync(d_in, scalars, count * 32, hipMemcpyHostToDevice, st) != hipSuccess) rc = KZGX_ERR_HIP;
+  if (rc == KZGX_OK) {
+    const dim3 grid((unsigned)((count + 63) / 64));
+    if (ctx->curve == KZGX_CURVE_BN254)
+      hipLaunchKernelGGL(k_joint_glv_debug<BN254G1>, grid, dim3(64), 0, st, d_in, (uint32_t)count, d_out);
+    else
+      hipLaunchKernelGGL(k_joint_glv_debug<BLS12381G1>, grid, dim3(64), 0, st, d_in, (uint32_t)count, d_out);
+    if (hipGetLastError() != hipSuccess) rc = KZGX_ERR_HIP;
+  }
+  if (rc == KZGX_OK && hipMemcpyAsync(out, d_out, count * 36, hipMemcpyDeviceToHost, st) != hipSuccess) rc = KZGX_ERR_HIP;
+  if (rc == KZGX_OK && hipStreamSynchronize(st) != hipSuccess) rc = KZGX_ERR_HIP;
+  (void)hipFree(d_in);
+  if (d_out) (void)hipFree(d_out);
+  return rc;
 }
 
 // device bring-up (kzgx_setup.hpp): one launch loads this code object

@@ -184,6 +184,14 @@ class proof {
                                                          std::vector<bool>* valid = nullptr);
 };
 
+/** Extension: one group of a batch opening (trusted_setup::create_batch_proofs):
+ *  the polynomials (or, for the verifier, the commitments) named by `polys`,
+ *  indices into the call's list, all opened at `point` under one proof. */
+struct batch_opening {
+  Fr point;
+  std::vector<uint32_t> polys;
+};
+
 class trusted_setup {
  private:
   kzgx_ctx* ctx = nullptr;  // device SRS + stream + workspaces
@@ -199,6 +207,9 @@ class trusted_setup {
                         bool checked, bool check_subgroup, std::vector<bool>* each = nullptr);
   std::vector<Fr> recovered(const std::vector<uint32_t>& cell_index, const std::vector<std::vector<Fr>>& values,
                             unsigned log2n, bool bit_reversed, std::vector<proof>* proofs);
+  bool batch_verified(std::vector<commit>& commits, const std::vector<batch_opening>& groups,
+                      const std::vector<Fr>& gammas, const std::vector<std::vector<Fr>>& values,
+                      std::vector<proof>& proofs, bool checked, bool check_subgroup);
 
  public:
   /** random tau (std::random_device), [tau^i]G1 and [tau^i]G2 for
@@ -450,6 +461,33 @@ class trusted_setup {
    *  commitments is the commitment of the combined polynomials.
    *  @throws std::invalid_argument on mismatched sizes */
   G1 linear_combination(const std::vector<G1>& points, const std::vector<Fr>& scalars);
+  /** Extension: batch openings (kzgx_prove_multi_batch with
+   *  KZGX_MULTI_WEIGHT_POWERS): ONE proof per group instead of one per
+   *  (polynomial, point) pair.  Proof g opens F_g = sum_j gammas[g]^j
+   *  polys[groups[g].polys[j]] at groups[g].point: one fold over the
+   *  coefficients and one MSM per group, all groups in one batched pipeline.
+   *  values_out (optional) receives, group by group in the order of `polys`
+   *  lists, every polynomial's own value at its group's point -- what the
+   *  verifier is told.  The caller derives the gammas (nothing is hashed here).
+   *  @throws std::invalid_argument on mismatched sizes, an index beyond
+   *          `polys`, or a degree beyond the setup */
+  std::vector<proof> create_batch_proofs(const std::vector<kzg::poly>& polys, const std::vector<batch_opening>& groups,
+                                         const std::vector<Fr>& gammas,
+                                         std::vector<std::vector<Fr>>* values_out = nullptr);
+  /** Extension: the verifier's side (kzgx_verify_multi_batch): `values[g][j]`
+   *  is the claimed value of commits[groups[g].polys[j]] at groups[g].point.
+   *  Two variable-base MSMs and ONE pairing check for the whole batch, under
+   *  library-drawn 128-bit challenges across the groups.  The second form runs
+   *  the G1 check of every commitment and proof first (check_subgroup: also
+   *  prime-order membership) and is false when one fails.  No groups: true.
+   *  @throws std::invalid_argument on mismatched sizes or an index beyond
+   *          `commits` */
+  bool verify_batch_proofs(std::vector<commit>& commits, const std::vector<batch_opening>& groups,
+                           const std::vector<Fr>& gammas, const std::vector<std::vector<Fr>>& values,
+                           std::vector<proof>& proofs);
+  bool verify_batch_proofs(std::vector<commit>& commits, const std::vector<batch_opening>& groups,
+                           const std::vector<Fr>& gammas, const std::vector<std::vector<Fr>>& values,
+                           std::vector<proof>& proofs, bool check_subgroup);
   /** copy of the G1 / G2 SRS points */
   std::vector<G1> g1_points() const;
   std::vector<G2> g2_points() const;

@@ -31,7 +31,9 @@
  * kzgx_verify_blobs_batch*, kzgx_verify_blobs_each* (flag KZGX_BLOB_BYTES): blob proofs --
  * the Fiat-Shamir challenge of a blob hashed on the device, the value of an
  * evaluation-form polynomial at any point, and blob-level prove / verify on 32-byte
- * big-endian scalars and compressed points.
+ * big-endian scalars and compressed points;
+ * kzgx_prove_multi_batch*, kzgx_verify_multi_batch*: batch openings -- many polynomials
+ * opened at shared points with one proof per point (both curves).
  *
  * Conventions
  *   - plain pointers and sizes only; no torch / HIP types in signatures
@@ -1154,6 +1156,133 @@ int kzgx_srs_verify_structure(kzgx_ctx* ctx, const uint64_t* rho, const uint64_t
  * As above, meaningful only for subgroup members (kzgx_g1_check_batch, kzgx_g2_check_batch). */
 int kzgx_srs_verify_update(kzgx_ctx* ctx, const uint64_t* prev_tau_g1_xy, const uint64_t* new_tau_g1_xy,
                            const uint64_t* witness_g2_xy, int* ok);
+
+/* ---- batch openings: many polynomials at shared points, one proof each (extensions) ----
+ * A prover that has committed to many polynomials opens them at the same few points and
+ * ships ONE proof per point, not one per (polynomial, point) pair: KZG is additively
+ * homomorphic, so the openings of a group at z are one opening of a weighted sum of the
+ * polynomials -- one Fr fold over the coefficients and one MSM per point.  Needs no
+ * evaluation domain and serves both curves.  No reference counterpart.
+ *
+ * Definitions.
+ *  - n_polys polynomials P_0 .. P_(n_polys-1) have n >= 1 coefficients each.  They are
+ *    canonical scalars.  Polynomial j sits at coeffs + j * coeff_stride (in scalars).
+ *    Shorter polynomials are zero-padded by the caller.
+ *  - n_groups groups.  Group g opens at the point z_g, which may be any canonical scalar.
+ *  - count claims, sorted by group.  The claims of group g are k in
+ *    [group_start[g], group_start[g+1]).
+ *     - group_start has n_groups + 1 uint32 entries and is non-decreasing.
+ *     - group_start[0] = 0 and group_start[n_groups] = count.
+ *     - Claim k names polynomial poly_index[k] on the prover side, or commitment
+ *       commit_index[k] on the verifier side.
+ *     - A polynomial may appear in several groups and more than once in one group.
+ *     - A group may be empty.
+ *  - Weights w_k, one canonical scalar per claim.
+ *     - With the flag KZGX_MULTI_WEIGHT_POWERS, weights holds one scalar gamma_g per group,
+ *       and w_k = gamma_g^(k - group_start[g]).  This is the usual "powers of a
+ *       Fiat-Shamir challenge".
+ *     - The library hashes nothing.  The caller derives gamma, as with every other
+ *       challenge in this library.
+ *  - F_g = sum_{k in g} w_k P_(poly_index[k]).
+ *  - y_k = P_(poly_index[k])(z_g).
+ *  - Y_g = sum_{k in g} w_k y_k = F_g(z_g).
+ *  - pi_g = [q_g(tau)]G1, where q_g = (F_g - Y_g) / (X - z_g).
+ *     - An empty group, or F_g constant, gives pi_g = infinity.
+ *  - Verifier, with challenges r_g (one per group) and commitments C_c:
+ *     - s_c = sum_{k : commit_index[k] = c} r_(g(k)) w_k
+ *     - t = sum_k r_(g(k)) w_k y_k
+ *     - *ok = e(sum_g r_g pi_g, G2[1]) == e(sum_c s_c C_c + sum_g (r_g z_g) pi_g - [t] G1[0], G2[0])
+ *     - This is exactly kzgx_verify_aggregate's equation on
+ *       (C'_g = sum w_k C_k, pi_g, z_g, Y_g, r_g).
+ *     - It costs two variable-base MSMs (n_groups points; n_commits + n_groups + 1 points)
+ *       and one two-pairing product, whatever count is.
+ *
+ * Prove.  out_xy / out_is_inf: the n_groups proofs; out_y (may be NULL): the count values
+ *  y_k; out_Y (may be NULL): the n_groups values Y_g.  Pipeline, per chunk of
+ *  max(1, KZGX_MULTI_CHUNK_SCALARS / n) groups (kzgx_set_multi_chunk changes the figure), at
+ *  most 65535 of them, the limit of the prove path: the fold kernel writes F_g into
+ *  workspace, then the unchanged kzgx_prove_single_batch_device(F, n, stride n, z, groups)
+ *  gives pi_g and Y_g -- one quotient launch and one batched MSM per chunk, never one per
+ *  claim, and the MSM on whatever path the context's table settings choose, as for any other
+ *  batch.  pi_g is bit for bit what kzgx_prove_single_batch returns for the polynomial F_g
+ *  at z_g.  The values y_k come from an evaluation kernel over the claims, in batches sized
+ *  by the same figure (the device entry cannot know which claims a chunk of groups holds
+ *  without reading group_start back, so the claims are walked on their own): a wavefront per
+ *  claim up to KZGX_MULTI_EVAL_SLICE coefficients, slices of KZGX_MULTI_EVAL_SLICE
+ *  coefficients per workgroup and a second small launch above.  Workspace per stream is
+ *  bounded by the chunk (max(chunk, n) scalars for F, as many for the quotients, and at most
+ *  max(chunk, n / KZGX_MULTI_EVAL_SLICE + 1) slice partials), not by count.
+ * Verify.  commits: n_commits canonical affine points; proofs: n_groups; ys: count values;
+ *  challenges: n_groups canonical scalars r_g.  The _checked forms run the
+ *  kzgx_g1_check_batch test over the n_commits commitments and the n_groups proofs first
+ *  and force *ok = 0 when a point fails, exactly as kzgx_verify_aggregate_checked does, with
+ *  the same subgroup argument.
+ *
+ * Host entries validate and return KZGX_ERR_ARG before any device work for: a NULL required
+ *  pointer, n == 0, coeff_stride < n, an unknown flag bit, a group_start that is not
+ *  non-decreasing from 0 to count, an index >= n_polys or >= n_commits, a z, weight or
+ *  challenge >= r, count or n_groups >= 2^31, n_commits + n_groups + 1 >
+ *  KZGX_MSM_POINTS_MAX.  challenges == NULL on the host verify draws independent 128-bit
+ *  values with r_0 = 1, as kzgx_verify_aggregate does.  weights == NULL is always
+ *  KZGX_ERR_ARG: the prover and the verifier must agree on the weights.
+ * Device entries are asynchronous on stream (NULL = the context's) and read nothing back
+ *  (n == 1 excepted: the prove path's empty MSM synchronises).  They check what the host can
+ *  see (pointers, sizes, flags).  An out-of-range index or a malformed group_start reads
+ *  nothing out of bounds: group ranges are clamped to [0, count], a claim with an index out
+ *  of range contributes nothing and its y_k is 0.  Such an input forces *d_ok = 0 (d_ok: one
+ *  uint32; on the prove side it may be NULL and reports only this validation).  NULL
+ *  challenges are KZGX_ERR_ARG.
+ * Other statuses: no SRS: KZGX_ERR_NO_SRS (the verify needs G1[0] and G2[0..1] only);
+ *  n - 1 larger than the SRS on the prove side: KZGX_ERR_DEGREE; n_groups == 0 (then count
+ *  must be 0): KZGX_OK with *ok = 1.
+ *
+ * Soundness.  With explicit weights and challenges the answer is a deterministic function
+ *  of the inputs: the equation above and nothing else.  A valid batch passes.  Errors can
+ *  cancel under weights or challenges the prover can predict (two wrong values +d and -d in
+ *  one group under equal weights pass; so do errors in two groups that cancel under the
+ *  given r), so gamma and r must come from a transcript that binds the commitments, the
+ *  points and the claimed values (gamma) and the proofs as well (r); with unpredictable
+ *  128-bit values a false claim passes with probability <= (claims per group + 1) / 2^128.
+ *  Points are taken as canonical and on the curve.  Subgroup membership is not checked here
+ *  on BLS12-381: that is the _checked forms' business, as for kzgx_verify_aggregate.
+ * Out of scope: openings of different polynomials at different point sets under one proof
+ *  (BDFG20, "Shplonk"); evaluation-form input (run kzgx_ntt_device first); any hashing of
+ *  transcripts; per-group verdicts (fold the commitments with kzgx_msm_g1_points and use
+ *  kzgx_verify_single_batch). */
+#define KZGX_MULTI_WEIGHT_POWERS 1 /* weights: one gamma_g per group, w_k = gamma_g^(k - group_start[g]) */
+#define KZGX_MULTI_CHUNK_SCALARS 2097152 /* scalars of folded polynomials per internal chunk */
+#define KZGX_MULTI_EVAL_SLICE 4096 /* coefficients per workgroup of the sliced evaluation */
+int kzgx_prove_multi_batch(kzgx_ctx* ctx, const uint64_t* coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                           const uint32_t* poly_index, const uint32_t* group_start, size_t n_groups,
+                           const uint64_t* zs, const uint64_t* weights, size_t count, int flags, uint64_t* out_xy,
+                           int* out_is_inf, uint64_t* out_y, uint64_t* out_Y);
+int kzgx_prove_multi_batch_device(kzgx_ctx* ctx, const void* d_coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                                  const void* d_poly_index, const void* d_group_start, size_t n_groups,
+                                  const void* d_zs, const void* d_weights, size_t count, int flags, void* d_out_xy,
+                                  void* d_out_is_inf, void* d_out_y, void* d_out_Y, void* d_ok, void* stream);
+int kzgx_verify_multi_batch(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                            const uint32_t* commit_index, const uint32_t* group_start, size_t n_groups,
+                            const uint64_t* zs, const uint64_t* ys, const uint64_t* weights,
+                            const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* challenges, size_t count,
+                            int flags, int* ok);
+int kzgx_verify_multi_batch_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, size_t n_commits,
+                                   const void* d_commit_index, const void* d_group_start, size_t n_groups,
+                                   const void* d_zs, const void* d_ys, const void* d_weights, const void* d_proofs,
+                                   const void* d_proof_inf, const void* d_challenges, size_t count, int flags,
+                                   void* d_ok, void* stream);
+int kzgx_verify_multi_batch_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf,
+                                    size_t n_commits, const uint32_t* commit_index, const uint32_t* group_start,
+                                    size_t n_groups, const uint64_t* zs, const uint64_t* ys, const uint64_t* weights,
+                                    const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* challenges,
+                                    size_t count, int flags, int subgroup, int* ok);
+int kzgx_verify_multi_batch_checked_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                           size_t n_commits, const void* d_commit_index, const void* d_group_start,
+                                           size_t n_groups, const void* d_zs, const void* d_ys,
+                                           const void* d_weights, const void* d_proofs, const void* d_proof_inf,
+                                           const void* d_challenges, size_t count, int flags, int subgroup,
+                                           void* d_ok, void* stream);
+/* test knob: scalars per internal chunk of the prove pipeline (0 restores KZGX_MULTI_CHUNK_SCALARS) */
+int kzgx_set_multi_chunk(kzgx_ctx* ctx, size_t scalars);
 
 #ifdef __cplusplus
 }

@@ -1274,6 +1274,126 @@ G1 trusted_setup::linear_combination(const std::vector<G1>& points, const std::v
   return to_g1(out.data(), oi != 0);
 }
 
+namespace {
+// groups -> the C ABI's flat claim list: index per claim, group_start, one point per group
+struct batch_claims {
+  std::vector<uint32_t> index, start;
+  std::vector<uint64_t> zs, gammas;
+};
+
+batch_claims flatten_groups(const std::vector<batch_opening>& groups, const std::vector<Fr>& gammas, size_t n_index,
+                            const char* who) {
+  if (gammas.size() != groups.size()) throw std::invalid_argument(std::string(who) + ": one gamma per group");
+  batch_claims c;
+  c.start.push_back(0);
+  for (size_t g = 0; g < groups.size(); g++) {
+    for (uint32_t j : groups[g].polys) {
+      if (j >= n_index) throw std::invalid_argument(std::string(who) + ": index out of range");
+      c.index.push_back(j);
+    }
+    c.start.push_back((uint32_t)c.index.size());
+    c.zs.insert(c.zs.end(), groups[g].point.v.begin(), groups[g].point.v.end());
+    c.gammas.insert(c.gammas.end(), gammas[g].v.begin(), gammas[g].v.end());
+  }
+  return c;
+}
+}  // namespace
+
+std::vector<proof> trusted_setup::create_batch_proofs(const std::vector<kzg::poly>& polys,
+                                                      const std::vector<batch_opening>& groups,
+                                                      const std::vector<Fr>& gammas,
+                                                      std::vector<std::vector<Fr>>* values_out) {
+  batch_claims cl = flatten_groups(groups, gammas, polys.size(), "create_batch_proofs");
+  std::vector<proof> res;
+  if (values_out) values_out->clear();
+  if (groups.empty()) return res;
+  size_t m = 1;  // zero-padded to a common length (the zero polynomial: one zero coefficient)
+  for (auto& p : polys) m = std::max(m, p.get_poly().size());
+  if (m - 1 > n) throw std::invalid_argument("polynomial degree be at most one less than the setup size (num_coeffs)");
+  std::vector<uint64_t> s(4 * m * std::max<size_t>(polys.size(), 1), 0);
+  for (size_t b = 0; b < polys.size(); b++) {
+    auto f = flat(polys[b].get_poly());
+    if (!f.empty()) std::memcpy(&s[4 * m * b], f.data(), f.size() * 8);
+  }
+  const int nl = base_limbs();
+  const size_t count = cl.index.size(), ng = groups.size();
+  std::vector<uint64_t> out(2 * nl * ng), y(4 * count + 4);
+  std::vector<int> inf(ng);
+  cl.index.push_back(0);  // never NULL
+  check(kzgx_prove_multi_batch(ctx, s.data(), m, m, polys.size(), cl.index.data(), cl.start.data(), ng, cl.zs.data(),
+                               cl.gammas.data(), count, KZGX_MULTI_WEIGHT_POWERS, out.data(), inf.data(),
+                               values_out ? y.data() : nullptr, nullptr),
+        "kzgx_prove_multi_batch");
+  for (size_t g = 0; g < ng; g++) res.push_back(proof(to_g1(&out[2 * nl * g], inf[g])));
+  if (values_out)
+    for (size_t g = 0; g < ng; g++) {
+      std::vector<Fr> v(cl.start[g + 1] - cl.start[g]);
+      for (size_t j = 0; j < v.size(); j++) std::memcpy(v[j].v.data(), &y[4 * (cl.start[g] + j)], 32);
+      values_out->push_back(std::move(v));
+    }
+  return res;
+}
+
+bool trusted_setup::verify_batch_proofs(std::vector<commit>& commits, const std::vector<batch_opening>& groups,
+                                        const std::vector<Fr>& gammas, const std::vector<std::vector<Fr>>& values,
+                                        std::vector<proof>& proofs) {
+  return batch_verified(commits, groups, gammas, values, proofs, false, false);
+}
+
+bool trusted_setup::verify_batch_proofs(std::vector<commit>& commits, const std::vector<batch_opening>& groups,
+                                        const std::vector<Fr>& gammas, const std::vector<std::vector<Fr>>& values,
+                                        std::vector<proof>& proofs, bool check_subgroup) {
+  return batch_verified(commits, groups, gammas, values, proofs, true, check_subgroup);
+}
+
+bool trusted_setup::batch_verified(std::vector<commit>& commits, const std::vector<batch_opening>& groups,
+                                   const std::vector<Fr>& gammas, const std::vector<std::vector<Fr>>& values,
+                                   std::vector<proof>& proofs, bool checked, bool check_subgroup) {
+  batch_claims cl = flatten_groups(groups, gammas, commits.size(), "verify_batch_proofs");
+  const size_t ng = groups.size(), nc = commits.size(), count = cl.index.size();
+  if (proofs.size() != ng || values.size() != ng) throw std::invalid_argument("verify_batch_proofs: size mismatch");
+  std::vector<uint64_t> y;
+  for (size_t g = 0; g < ng; g++) {
+    if (values[g].size() != groups[g].polys.size())
+      throw std::invalid_argument("verify_batch_proofs: one value per opened commitment");
+    for (auto& v : values[g]) y.insert(y.end(), v.v.begin(), v.v.end());
+  }
+  if (ng == 0) return true;
+  const int nl = base_limbs();
+  std::vector<uint64_t> c(2 * nl * nc + 1, 0), p(2 * nl * ng, 0);
+  std::vector<int> ci(nc + 1), pi(ng);
+  for (size_t k = 0; k < nc; k++) {
+    const G1& cg = commits[k].get_curve_point();
+    for (int i = 0; i < nl; i++) {
+      c[2 * nl * k + i] = cg.x[i];
+      c[2 * nl * k + nl + i] = cg.y[i];
+    }
+    ci[k] = cg.inf;
+  }
+  for (size_t g = 0; g < ng; g++) {
+    const G1& pg = proofs[g].get_curve_point();
+    for (int i = 0; i < nl; i++) {
+      p[2 * nl * g + i] = pg.x[i];
+      p[2 * nl * g + nl + i] = pg.y[i];
+    }
+    pi[g] = pg.inf;
+  }
+  cl.index.push_back(0);  // never NULL
+  y.resize(y.size() + 4);
+  int ok = 0;
+  if (checked)
+    check(kzgx_verify_multi_batch_checked(ctx, c.data(), ci.data(), nc, cl.index.data(), cl.start.data(), ng,
+                                          cl.zs.data(), y.data(), cl.gammas.data(), p.data(), pi.data(), nullptr,
+                                          count, KZGX_MULTI_WEIGHT_POWERS, check_subgroup ? 1 : 0, &ok),
+          "kzgx_verify_multi_batch_checked");
+  else
+    check(kzgx_verify_multi_batch(ctx, c.data(), ci.data(), nc, cl.index.data(), cl.start.data(), ng, cl.zs.data(),
+                                  y.data(), cl.gammas.data(), p.data(), pi.data(), nullptr, count,
+                                  KZGX_MULTI_WEIGHT_POWERS, &ok),
+          "kzgx_verify_multi_batch");
+  return ok != 0;
+}
+
 std::vector<G1> trusted_setup::g1_points() const {
   const int nl = base_limbs();
   std::vector<uint64_t> xy(2 * nl * n);

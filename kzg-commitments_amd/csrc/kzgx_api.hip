@@ -23,6 +23,7 @@
 #include "fr_host.hpp"
 #include "kzgx_internal.hpp"
 #include "kzgx_setup.hpp"
+#include "multi_open.hpp"
 
 // a generated G2 SRS of at most this many points gets its polyeval_G2 window
 // table at setup (kzgx_gen_srs_g2); larger ones on first use
@@ -62,6 +63,11 @@ struct kzgx_ctx {
   // the blob entries' buffers (decoded limbs, recovered points, z, y, flags), per slot as d_chk
   uint32_t* d_blob[kzgx::KZGX_MAX_STREAMS] = {};
   size_t blob_b[kzgx::KZGX_MAX_STREAMS] = {};
+  // the batch openings' buffers (a chunk's folded polynomials, the sliced evaluation's partials, the
+  // verifier's gate word), per slot as d_chk; multi_chunk: scalars per chunk (0 = KZGX_MULTI_CHUNK_SCALARS)
+  uint32_t* d_multi[kzgx::KZGX_MAX_STREAMS] = {};
+  size_t multi_b[kzgx::KZGX_MAX_STREAMS] = {};
+  size_t multi_chunk = 0;
 
   // pinned, device-mapped host staging for the host-pointer entry points
   // (kzgx_msm_g1_batch, kzgx_prove_single_batch): inputs are copied into it
@@ -626,6 +632,8 @@ void kzgx_destroy(kzgx_ctx* ctx) {
   for (void* p : ctx->d_chk)
     if (p) (void)hipFree(p);
   for (void* p : ctx->d_blob)
+    if (p) (void)hipFree(p);
+  for (void* p : ctx->d_multi)
     if (p) (void)hipFree(p);
   for (auto& f : c.fk) {
     if (f.x) (void)hipFree(f.x);
@@ -3654,6 +3662,327 @@ int kzgx_srs_verify_update(kzgx_ctx* ctx, const uint64_t* prev_tau_g1_xy, const 
             ? 1
             : 0;
   return KZGX_OK;
+}
+
+}  // extern "C"
+
+// ---- batch openings: many polynomials at shared points, one proof each (multi_open.hip) ----------
+namespace {
+// the batch openings' buffer of the workspace slot leased for this call's stream
+int multi_scratch(kzgx_ctx* ctx, const kzgx::WsLease& ws, size_t bytes, uint32_t** out) {
+  const size_t slot = (size_t)(ws.get() - ctx->c.ws);
+  KZGX_TRY(kzgx::dev_alloc(&ctx->c, (void**)&ctx->d_multi[slot], bytes, &ctx->multi_b[slot]));
+  *out = ctx->d_multi[slot];
+  return KZGX_OK;
+}
+
+// what the host can see of a call's shape, both sides (n_index: polynomials or commitments)
+bool multi_shape_ok(size_t n_index, size_t n_groups, size_t count, int flags) {
+  return (flags & ~KZGX_MULTI_WEIGHT_POWERS) == 0 && n_index <= 0xffffffffu && n_groups <= 0x7fffffffu &&
+         count <= 0x7fffffffu && (n_groups > 0 || count == 0);
+}
+
+// the host entries' structure check: group_start non-decreasing from 0 to count, every index in range
+bool multi_structure_ok(const uint32_t* index, size_t n_index, const uint32_t* group_start, size_t n_groups,
+                        size_t count) {
+  if (group_start[0] != 0 || group_start[n_groups] != count) return false;
+  for (size_t g = 0; g < n_groups; g++)
+    if (group_start[g] > group_start[g + 1]) return false;
+  for (size_t k = 0; k < count; k++)
+    if (index[k] >= n_index) return false;
+  return true;
+}
+
+bool multi_canonical(int curve, const uint64_t* v, size_t m) {
+  for (size_t i = 0; i < m; i++)
+    if (!fr_in_range(curve, v + 4 * i, true)) return false;
+  return true;
+}
+
+size_t align32(size_t b) { return (b + 31) & ~(size_t)31; }
+}  // namespace
+
+extern "C" {
+
+int kzgx_set_multi_chunk(kzgx_ctx* ctx, size_t scalars) {
+  if (!ctx) return KZGX_ERR_ARG;
+  ctx->multi_chunk = scalars;
+  return KZGX_OK;
+}
+
+int kzgx_prove_multi_batch_device(kzgx_ctx* ctx, const void* d_coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                                  const void* d_poly_index, const void* d_group_start, size_t n_groups,
+                                  const void* d_zs, const void* d_weights, size_t count, int flags, void* d_out_xy,
+                                  void* d_out_is_inf, void* d_out_y, void* d_out_Y, void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (!multi_shape_ok(n_polys, n_groups, count, flags) || n == 0 || n > 0xffffffffu || coeff_stride < n)
+    return KZGX_ERR_ARG;
+  if (n_groups > 0 && (!d_coeffs || !d_group_start || !d_zs || !d_weights || !d_out_xy || !d_out_is_inf ||
+                       (count > 0 && !d_poly_index)))
+    return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  if (n - 1 > ctx->c.n_srs) return KZGX_ERR_DEGREE;
+  hipStream_t st = pick(ctx, stream);
+  if (n_groups == 0) {
+    if (d_ok) KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)d_ok, 1, 1, st));
+    return KZGX_OK;
+  }
+  kzgx::Ctx* c = &ctx->c;
+  kzgx::WsLease ws = c->ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const bool powers = (flags & KZGX_MULTI_WEIGHT_POWERS) != 0;
+  const size_t chunk = ctx->multi_chunk ? ctx->multi_chunk : kzgx::MULTI_CHUNK_SCALARS;
+  // groups per chunk (65535: the prove path's batch limit); claims per evaluation batch
+  const size_t cg = std::min<size_t>({std::max<size_t>(1, chunk / n), 65535, n_groups});
+  const uint32_t slice = kzgx::MULTI_EVAL_SLICE;
+  const size_t nsl = n > slice ? (n + slice - 1) / slice : 0;
+  const bool want_y = d_out_y && count > 0;
+  const size_t ek = !want_y ? 0 : nsl ? std::min(std::max<size_t>(1, chunk / nsl), count) : count;
+  const size_t part_sc = want_y ? kzgx::multi_eval_part_scalars(ek, n, slice) : 0;
+  uint32_t* F;
+  KZGX_TRY(multi_scratch(ctx, ws, (cg * n + part_sc) * 32, &F));
+  uint32_t* part = F + cg * n * 8;
+  const uint32_t* gs = (const uint32_t*)d_group_start;
+  const uint32_t* pidx = (const uint32_t*)d_poly_index;
+  if (d_ok) KZGX_TRY(kzgx::multi_check(c, pidx, n_polys, gs, n_groups, count, (uint32_t*)d_ok, st));
+  const size_t pb = point_words(ctx) * 4;
+  for (size_t g0 = 0; g0 < n_groups; g0 += cg) {
+    const size_t ng = std::min(cg, n_groups - g0);
+    KZGX_TRY(kzgx::multi_fold(c, (const uint32_t*)d_coeffs, n, coeff_stride * 8, n_polys, pidx, gs, g0, ng, count,
+                              (const uint32_t*)d_weights, powers, F, st));
+    KZGX_TRY(kzgx_prove_single_batch_device(ctx, F, n, n, (const char*)d_zs + g0 * 32, ng, (char*)d_out_xy + g0 * pb,
+                                            (char*)d_out_is_inf + g0 * 4,
+                                            d_out_Y ? (char*)d_out_Y + g0 * 32 : nullptr, st));
+  }
+  for (size_t k0 = 0; want_y && k0 < count; k0 += ek)
+    KZGX_TRY(kzgx::multi_eval(c, (const uint32_t*)d_coeffs, n, coeff_stride * 8, n_polys, pidx, gs, n_groups,
+                              (const uint32_t*)d_zs, k0, std::min(ek, count - k0), (uint32_t*)d_out_y, part, slice,
+                              st));
+  return KZGX_OK;
+}
+
+int kzgx_prove_multi_batch(kzgx_ctx* ctx, const uint64_t* coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                           const uint32_t* poly_index, const uint32_t* group_start, size_t n_groups,
+                           const uint64_t* zs, const uint64_t* weights, size_t count, int flags, uint64_t* out_xy,
+                           int* out_is_inf, uint64_t* out_y, uint64_t* out_Y) {
+  KZGX_TRY(activate(ctx));
+  if (!multi_shape_ok(n_polys, n_groups, count, flags) || n == 0 || n > 0xffffffffu || coeff_stride < n)
+    return KZGX_ERR_ARG;
+  const size_t nw = (flags & KZGX_MULTI_WEIGHT_POWERS) ? n_groups : count;
+  if (n_groups > 0) {
+    if (!group_start || !zs || !weights || !out_xy || !out_is_inf || (count > 0 && !poly_index) ||
+        (n_polys > 0 && !coeffs))
+      return KZGX_ERR_ARG;
+    if (!multi_structure_ok(poly_index, n_polys, group_start, n_groups, count) ||
+        !multi_canonical(ctx->c.curve, zs, n_groups) || !multi_canonical(ctx->c.curve, weights, nw))
+      return KZGX_ERR_ARG;
+  }
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  if (n - 1 > ctx->c.n_srs) return KZGX_ERR_DEGREE;
+  if (n_groups == 0) return KZGX_OK;
+  const size_t pb = point_words(ctx) * 4;
+  const size_t cb = n_polys ? ((n_polys - 1) * coeff_stride + n) * 32 : 32;
+  // inputs: z | weights | poly_index | group_start; outputs: proofs | y | Y | flags
+  const size_t i_w = n_groups * 32, i_p = i_w + nw * 32, i_g = i_p + align32(count * 4),
+               i_end = i_g + (n_groups + 1) * 4;
+  const size_t o_y = align32(n_groups * pb), o_Y = o_y + count * 32, o_f = o_Y + n_groups * 32,
+               o_end = o_f + n_groups * 4;
+  void *d_c, *d_i, *d_o;
+  KZGX_TRY(stage(ctx, 0, cb, &d_c));
+  KZGX_TRY(stage(ctx, 1, i_end, &d_i));
+  KZGX_TRY(stage(ctx, 2, o_end, &d_o));
+  hipStream_t st = ctx->c.stream;
+  char *in = (char*)d_i, *out = (char*)d_o;
+  if (n_polys) KZGX_TRY_HIP(hipMemcpyAsync(d_c, coeffs, cb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(in, zs, n_groups * 32, hipMemcpyHostToDevice, st));
+  if (nw) KZGX_TRY_HIP(hipMemcpyAsync(in + i_w, weights, nw * 32, hipMemcpyHostToDevice, st));
+  if (count) KZGX_TRY_HIP(hipMemcpyAsync(in + i_p, poly_index, count * 4, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(in + i_g, group_start, (n_groups + 1) * 4, hipMemcpyHostToDevice, st));
+  KZGX_TRY(kzgx_prove_multi_batch_device(ctx, d_c, n, coeff_stride, n_polys, in + i_p, in + i_g, n_groups, in,
+                                         in + i_w, count, flags, out, out + o_f, out_y ? out + o_y : nullptr,
+                                         out_Y ? out + o_Y : nullptr, nullptr, nullptr));
+  std::vector<uint32_t> inf(n_groups);
+  KZGX_TRY_HIP(hipMemcpyAsync(out_xy, out, n_groups * pb, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(inf.data(), out + o_f, n_groups * 4, hipMemcpyDeviceToHost, st));
+  if (out_y && count) KZGX_TRY_HIP(hipMemcpyAsync(out_y, out + o_y, count * 32, hipMemcpyDeviceToHost, st));
+  if (out_Y) KZGX_TRY_HIP(hipMemcpyAsync(out_Y, out + o_Y, n_groups * 32, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  for (size_t g = 0; g < n_groups; g++) out_is_inf[g] = (int)inf[g];
+  return KZGX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the device verify, with the point checks in front when checked
+int verify_multi_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, size_t n_commits,
+                        const void* d_commit_index, const void* d_group_start, size_t n_groups, const void* d_zs,
+                        const void* d_ys, const void* d_weights, const void* d_proofs, const void* d_proof_inf,
+                        const void* d_challenges, size_t count, int flags, bool checked, int subgroup, void* d_ok,
+                        void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (!multi_shape_ok(n_commits, n_groups, count, flags) || !d_ok) return KZGX_ERR_ARG;
+  if (n_groups > 0 && (!d_challenges || !d_weights || !d_group_start || !d_zs || !d_proofs ||
+                       (n_commits > 0 && !d_commits) || (count > 0 && (!d_commit_index || !d_ys))))
+    return KZGX_ERR_ARG;
+  if (n_commits + n_groups + 1 > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0 || ctx->n_srs2 < 2) return KZGX_ERR_NO_SRS;
+  hipStream_t st = pick(ctx, stream);
+  if (n_groups == 0) {
+    KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)d_ok, 1, 1, st));
+    return KZGX_OK;
+  }
+  kzgx::Ctx* c = &ctx->c;
+  kzgx::WsLease ws = c->ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const size_t pw = point_words(ctx);
+  uint32_t* f = nullptr;  // commit flags | proof flags | their AND
+  if (checked) {
+    KZGX_TRY(chk_scratch(ctx, ws, n_commits + n_groups + 1, &f));
+    if (n_commits)
+      KZGX_TRY(kzgx::g1_check2(c, (const uint32_t*)d_commits, (const uint32_t*)d_commit_inf, n_commits,
+                               (const uint32_t*)d_proofs, (const uint32_t*)d_proof_inf, n_groups, subgroup, f, st));
+    else
+      KZGX_TRY(kzgx::g1_check(c, (const uint32_t*)d_proofs, (const uint32_t*)d_proof_inf, n_groups, subgroup, f, st));
+    KZGX_TRY(kzgx::flags_and(f, n_commits + n_groups, f + n_commits + n_groups, st));
+  }
+  // scalars s_c | r_g z_g | -t (+ scratch); A | B | flags [A_inf, B_inf, gate, -] | z = y = 0
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->var_scal, kzgx::multi_scalars_words(n_commits, n_groups, count) * 4,
+                           &ws->var_scal_b));
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->var_pt, (2 * pw + 4 + 16) * 4, &ws->var_pt_b));
+  uint32_t* A = ws->var_pt;
+  uint32_t* B = A + pw;
+  uint32_t* fl = B + pw;
+  uint32_t* zero = fl + 4;
+  KZGX_TRY_HIP(hipMemsetAsync(zero, 0, 64, st));
+  KZGX_TRY(kzgx::multi_check(c, (const uint32_t*)d_commit_index, n_commits, (const uint32_t*)d_group_start, n_groups,
+                             count, fl + 2, st));
+  KZGX_TRY(kzgx::multi_scalars(c, (const uint32_t*)d_commit_index, (const uint32_t*)d_group_start, n_groups,
+                               (const uint32_t*)d_zs, (const uint32_t*)d_ys, (const uint32_t*)d_weights,
+                               (flags & KZGX_MULTI_WEIGHT_POWERS) != 0, (const uint32_t*)d_challenges, count,
+                               n_commits, ws->var_scal, st));
+  // A = sum r_g proof_g
+  const kzgx::PointSeg sa{(const uint32_t*)d_proofs, (const uint32_t*)d_proof_inf, n_groups};
+  KZGX_TRY(kzgx::msm_points(c, *ws, &sa, 1, (const uint32_t*)d_challenges, A, fl, st));
+  // B = sum s_c commit_c + sum r_g z_g proof_g - t G1[0]
+  const kzgx::PointSeg sb[3] = {{(const uint32_t*)d_commits, (const uint32_t*)d_commit_inf, n_commits},
+                                {(const uint32_t*)d_proofs, (const uint32_t*)d_proof_inf, n_groups},
+                                {ctx->d_srs_canon, nullptr, 1}};
+  const int skip = n_commits ? 0 : 1;  // no empty segment
+  KZGX_TRY(kzgx::msm_points(c, *ws, sb + skip, 3 - skip, ws->var_scal, B, fl + 1, st));
+  // e(A, [tau]G2) == e(B, G2[0]), as kzgx_verify_aggregate_device's tail
+  KZGX_TRY(kzgx_verify_single_batch_device(ctx, B, fl + 1, A, fl, zero, zero + 8, 1, d_ok, stream));
+  KZGX_TRY(kzgx::flag_gate((uint32_t*)d_ok, fl + 2, st));
+  if (checked) KZGX_TRY(kzgx::flag_gate((uint32_t*)d_ok, f + n_commits + n_groups, st));
+  return KZGX_OK;
+}
+
+int verify_multi_host(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                      const uint32_t* commit_index, const uint32_t* group_start, size_t n_groups, const uint64_t* zs,
+                      const uint64_t* ys, const uint64_t* weights, const uint64_t* proofs_xy, const int* proof_inf,
+                      const uint64_t* challenges, size_t count, int flags, bool checked, int subgroup, int* ok) {
+  KZGX_TRY(activate(ctx));
+  if (!multi_shape_ok(n_commits, n_groups, count, flags) || !ok) return KZGX_ERR_ARG;
+  const int curve = ctx->c.curve;
+  const size_t nw = (flags & KZGX_MULTI_WEIGHT_POWERS) ? n_groups : count;
+  if (n_groups > 0) {
+    if (!weights || !group_start || !zs || !proofs_xy || (n_commits > 0 && !commits_xy) ||
+        (count > 0 && (!commit_index || !ys)))
+      return KZGX_ERR_ARG;
+    if (!multi_structure_ok(commit_index, n_commits, group_start, n_groups, count) ||
+        !multi_canonical(curve, zs, n_groups) || !multi_canonical(curve, weights, nw) || (challenges && !multi_canonical(curve, challenges, n_groups)))
+      return KZGX_ERR_ARG;
+  }
+  if (n_commits + n_groups + 1 > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0 || ctx->n_srs2 < 2) return KZGX_ERR_NO_SRS;
+  if (n_groups == 0) {
+    *ok = 1;
+    return KZGX_OK;
+  }
+  // library-drawn challenges: independent 128-bit values, r_0 = 1 (as kzgx_verify_aggregate)
+  std::vector<uint64_t> drawn;
+  if (!challenges) {
+    drawn.assign(n_groups * 4, 0);
+    std::random_device rd;
+    for (size_t g = 0; g < n_groups; g++)
+      for (int j = 0; j < 2; j++) drawn[4 * g + j] = ((uint64_t)rd() << 32) | (uint64_t)rd();
+    drawn[0] = 1;
+    drawn[1] = 0;
+    challenges = drawn.data();
+  }
+  const size_t pb = point_words(ctx) * 4;
+  // scalars: z | y | weights | challenges; words: commit_inf | proof_inf | commit_index | group_start | ok
+  const size_t s_y = n_groups * 32, s_w = s_y + count * 32, s_r = s_w + nw * 32, s_end = s_r + n_groups * 32;
+  const size_t w_p = n_commits, w_i = w_p + n_groups, w_g = w_i + count, w_ok = w_g + n_groups + 1;
+  void *d_c, *d_p, *d_s, *d_w;
+  KZGX_TRY(stage(ctx, 0, n_commits * pb, &d_c));
+  KZGX_TRY(stage(ctx, 1, n_groups * pb, &d_p));
+  KZGX_TRY(stage(ctx, 2, s_end, &d_s));
+  KZGX_TRY(stage(ctx, 3, (w_ok + 1) * 4, &d_w));
+  std::vector<uint32_t> w(w_ok, 0u);
+  for (size_t i = 0; i < n_commits; i++) w[i] = commit_inf ? (uint32_t)(commit_inf[i] != 0) : 0u;
+  for (size_t g = 0; g < n_groups; g++) w[w_p + g] = proof_inf ? (uint32_t)(proof_inf[g] != 0) : 0u;
+  std::copy(commit_index, commit_index + count, w.begin() + w_i);
+  std::copy(group_start, group_start + n_groups + 1, w.begin() + w_g);
+  hipStream_t st = ctx->c.stream;
+  char* sc = (char*)d_s;
+  uint32_t* dw = (uint32_t*)d_w;
+  if (n_commits) KZGX_TRY_HIP(hipMemcpyAsync(d_c, commits_xy, n_commits * pb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_p, proofs_xy, n_groups * pb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(sc, zs, n_groups * 32, hipMemcpyHostToDevice, st));
+  if (count) KZGX_TRY_HIP(hipMemcpyAsync(sc + s_y, ys, count * 32, hipMemcpyHostToDevice, st));
+  if (nw) KZGX_TRY_HIP(hipMemcpyAsync(sc + s_w, weights, nw * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(sc + s_r, challenges, n_groups * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(dw, w.data(), w_ok * 4, hipMemcpyHostToDevice, st));
+  KZGX_TRY(verify_multi_device(ctx, d_c, dw, n_commits, dw + w_i, dw + w_g, n_groups, sc, sc + s_y, sc + s_w, d_p,
+                               dw + w_p, sc + s_r, count, flags, checked, subgroup, dw + w_ok, nullptr));
+  uint32_t v = 0;
+  KZGX_TRY_HIP(hipMemcpyAsync(&v, dw + w_ok, 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  *ok = v ? 1 : 0;
+  return KZGX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kzgx_verify_multi_batch_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, size_t n_commits,
+                                   const void* d_commit_index, const void* d_group_start, size_t n_groups,
+                                   const void* d_zs, const void* d_ys, const void* d_weights, const void* d_proofs,
+                                   const void* d_proof_inf, const void* d_challenges, size_t count, int flags,
+                                   void* d_ok, void* stream) {
+  return verify_multi_device(ctx, d_commits, d_commit_inf, n_commits, d_commit_index, d_group_start, n_groups, d_zs,
+                             d_ys, d_weights, d_proofs, d_proof_inf, d_challenges, count, flags, false, 0, d_ok,
+                             stream);
+}
+
+int kzgx_verify_multi_batch_checked_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                           size_t n_commits, const void* d_commit_index, const void* d_group_start,
+                                           size_t n_groups, const void* d_zs, const void* d_ys,
+                                           const void* d_weights, const void* d_proofs, const void* d_proof_inf,
+                                           const void* d_challenges, size_t count, int flags, int subgroup,
+                                           void* d_ok, void* stream) {
+  return verify_multi_device(ctx, d_commits, d_commit_inf, n_commits, d_commit_index, d_group_start, n_groups, d_zs,
+                             d_ys, d_weights, d_proofs, d_proof_inf, d_challenges, count, flags, true, subgroup, d_ok,
+                             stream);
+}
+
+int kzgx_verify_multi_batch(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                            const uint32_t* commit_index, const uint32_t* group_start, size_t n_groups,
+                            const uint64_t* zs, const uint64_t* ys, const uint64_t* weights,
+                            const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* challenges, size_t count,
+                            int flags, int* ok) {
+  return verify_multi_host(ctx, commits_xy, commit_inf, n_commits, commit_index, group_start, n_groups, zs, ys,
+                           weights, proofs_xy, proof_inf, challenges, count, flags, false, 0, ok);
+}
+
+int kzgx_verify_multi_batch_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf,
+                                    size_t n_commits, const uint32_t* commit_index, const uint32_t* group_start,
+                                    size_t n_groups, const uint64_t* zs, const uint64_t* ys, const uint64_t* weights,
+                                    const uint64_t* proofs_xy, const int* proof_inf, const uint64_t* challenges,
+                                    size_t count, int flags, int subgroup, int* ok) {
+  return verify_multi_host(ctx, commits_xy, commit_inf, n_commits, commit_index, group_start, n_groups, zs, ys,
+                           weights, proofs_xy, proof_inf, challenges, count, flags, true, subgroup, ok);
 }
 
 }  // extern "C"

@@ -56,6 +56,9 @@ EXPORTS = [
     "kzgx_verify_blobs_batch", "kzgx_verify_blobs_batch_device", "kzgx_verify_blobs_each",
     "kzgx_verify_blobs_each_device",
     "kzgx_srs_update", "kzgx_srs_verify_structure", "kzgx_srs_verify_update",
+    "kzgx_prove_multi_batch", "kzgx_prove_multi_batch_device", "kzgx_verify_multi_batch",
+    "kzgx_verify_multi_batch_device", "kzgx_verify_multi_batch_checked", "kzgx_verify_multi_batch_checked_device",
+    "kzgx_set_multi_chunk",
 ]
 
 
@@ -89,6 +92,11 @@ BLOB_BYTES = _header_define("KZGX_BLOB_BYTES")
 BLOB_CHUNK_SCALARS = _header_define("KZGX_BLOB_CHUNK_SCALARS")
 # setup ceremony: the structure test also requires G1[0], G2[0] to be the curve's generators
 SRS_STRUCT_GENERATORS = _header_define("KZGX_SRS_STRUCT_GENERATORS")
+# batch openings: weights are one gamma per group, the scalars per internal chunk of folded
+# polynomials, and the coefficients per workgroup of the sliced evaluation
+MULTI_WEIGHT_POWERS = _header_define("KZGX_MULTI_WEIGHT_POWERS")
+MULTI_CHUNK_SCALARS = _header_define("KZGX_MULTI_CHUNK_SCALARS")
+MULTI_EVAL_SLICE = _header_define("KZGX_MULTI_EVAL_SLICE")
 
 _lib = None
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -289,6 +297,20 @@ def lib():
             "kzgx_srs_update": (ctypes.c_int, [vp, u64p, sz, sz, u64p]),
             "kzgx_srs_verify_structure": (ctypes.c_int, [vp, u64p, u64p, ctypes.c_int, intp, intp]),
             "kzgx_srs_verify_update": (ctypes.c_int, [vp, u64p, u64p, u64p, intp]),
+            "kzgx_prove_multi_batch": (ctypes.c_int, [vp, u64p, sz, sz, sz, u32p, u32p, sz, u64p, u64p, sz,
+                                                      ctypes.c_int, u64p, intp, u64p, u64p]),
+            "kzgx_prove_multi_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, vp, sz, vp, vp, sz, ctypes.c_int,
+                                                             vp, vp, vp, vp, vp, vp]),
+            "kzgx_verify_multi_batch": (ctypes.c_int, [vp, u64p, intp, sz, u32p, u32p, sz, u64p, u64p, u64p, u64p,
+                                                       intp, u64p, sz, ctypes.c_int, intp]),
+            "kzgx_verify_multi_batch_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz,
+                                                              ctypes.c_int, vp, vp]),
+            "kzgx_verify_multi_batch_checked": (ctypes.c_int, [vp, u64p, intp, sz, u32p, u32p, sz, u64p, u64p, u64p,
+                                                               u64p, intp, u64p, sz, ctypes.c_int, ctypes.c_int,
+                                                               intp]),
+            "kzgx_verify_multi_batch_checked_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp,
+                                                                      vp, sz, ctypes.c_int, ctypes.c_int, vp, vp]),
+            "kzgx_set_multi_chunk": (ctypes.c_int, [vp, sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -964,6 +986,88 @@ class Context:
         _chk(lib().kzgx_verify_aggregate_checked_device(self.h, d_commits, d_commit_inf, d_proofs, d_proof_inf, d_z,
                                                         d_y, d_challenges, count, int(bool(subgroup)), d_ok, stream),
              "kzgx_verify_aggregate_checked_device")
+
+    # ---- batch openings: many polynomials at shared points, one proof each ----
+    def prove_multi(self, polys, poly_index, group_start, zs, weights, powers: bool = False, n: int | None = None,
+                    want_y: bool = True):
+        """kzgx_prove_multi_batch.  polys: (n_polys, stride, 4), the first n coefficients of a row used (n = stride
+        by default); claim k names polys[poly_index[k]], group g holds the claims group_start[g] .. group_start[g+1]
+        and opens at zs[g]; weights: one scalar per claim, or one gamma per group with powers.  Returns the
+        n_groups proofs, their infinity flags, the count values y_k (None without want_y) and the n_groups Y_g."""
+        c = np.ascontiguousarray(polys, dtype=np.uint64)
+        assert c.ndim == 3 and c.shape[2] == 4
+        n_polys, stride = c.shape[0], c.shape[1]
+        n = stride if n is None else n
+        pi = np.ascontiguousarray(poly_index, dtype=np.uint32).reshape(-1)
+        gs = np.ascontiguousarray(group_start, dtype=np.uint32).reshape(-1)
+        count, n_groups = pi.shape[0], gs.shape[0] - 1
+        z = as_scalars(zs) if n_groups else np.zeros((0, 4), dtype=np.uint64)
+        w = np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1, 4)
+        assert z.shape[0] == n_groups and w.shape[0] == (n_groups if powers else count)
+        out = np.zeros((n_groups, 2 * self.w64), dtype=np.uint64)
+        inf = np.zeros(n_groups, dtype=np.int32)
+        y = np.zeros((count, 4), dtype=np.uint64) if want_y else None
+        Y = np.zeros((n_groups, 4), dtype=np.uint64)
+        _chk(lib().kzgx_prove_multi_batch(self.h, _p(c), n, stride, n_polys, pi.ctypes.data_as(u32p),
+                                          gs.ctypes.data_as(u32p), n_groups, _p(z), _p(w), count,
+                                          MULTI_WEIGHT_POWERS if powers else 0, _p(out), inf.ctypes.data_as(intp),
+                                          _p(y), _p(Y)), "kzgx_prove_multi_batch")
+        return out, inf.astype(bool), y, Y
+
+    def prove_multi_device(self, d_coeffs, n, stride, n_polys, d_poly_index, d_group_start, n_groups, d_zs, d_weights,
+                           count, d_out, d_inf, d_y=None, d_Y=None, d_ok=None, powers=False, stream=None):
+        """kzgx_prove_multi_batch_device: device pointers (indices uint32), d_ok one uint32 or None, enqueued on
+        stream."""
+        _chk(lib().kzgx_prove_multi_batch_device(self.h, d_coeffs, n, stride, n_polys, d_poly_index, d_group_start,
+                                                 n_groups, d_zs, d_weights, count,
+                                                 MULTI_WEIGHT_POWERS if powers else 0, d_out, d_inf, d_y, d_Y, d_ok,
+                                                 stream), "kzgx_prove_multi_batch_device")
+
+    def verify_multi(self, commits, commit_index, group_start, zs, ys, weights, proofs, challenges=None,
+                     powers: bool = False, commit_inf=None, proof_inf=None, checked: bool = False,
+                     subgroup: int = 0) -> bool:
+        """kzgx_verify_multi_batch(_checked): one pairing check of the n_groups proofs against the count claimed
+        values ys of the commitments commits[commit_index[k]]; challenges: one scalar per group, None = the
+        library draws 128-bit values (r_0 = 1); checked: the G1 check of every commitment and proof in front."""
+        c = np.ascontiguousarray(commits, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        p = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        ci = np.ascontiguousarray(commit_index, dtype=np.uint32).reshape(-1)
+        gs = np.ascontiguousarray(group_start, dtype=np.uint32).reshape(-1)
+        count, n_groups, n_commits = ci.shape[0], gs.shape[0] - 1, c.shape[0]
+        z = as_scalars(zs) if n_groups else np.zeros((0, 4), dtype=np.uint64)
+        y = as_scalars(ys) if count else np.zeros((0, 4), dtype=np.uint64)
+        w = np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1, 4)
+        r = None if challenges is None else np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1, 4)
+        assert p.shape[0] == n_groups and z.shape[0] == n_groups and y.shape[0] == count
+        assert w.shape[0] == (n_groups if powers else count) and (r is None or r.shape[0] == n_groups)
+        fc = None if commit_inf is None else np.ascontiguousarray(commit_inf, dtype=np.int32)
+        fp = None if proof_inf is None else np.ascontiguousarray(proof_inf, dtype=np.int32)
+        ok = ctypes.c_int(0)
+        args = [self.h, _p(c), None if fc is None else fc.ctypes.data_as(intp), n_commits, ci.ctypes.data_as(u32p),
+                gs.ctypes.data_as(u32p), n_groups, _p(z), _p(y), _p(w), _p(p),
+                None if fp is None else fp.ctypes.data_as(intp), _p(r), count, MULTI_WEIGHT_POWERS if powers else 0]
+        if checked:
+            _chk(lib().kzgx_verify_multi_batch_checked(*args, int(bool(subgroup)), ctypes.byref(ok)),
+                 "kzgx_verify_multi_batch_checked")
+        else:
+            _chk(lib().kzgx_verify_multi_batch(*args, ctypes.byref(ok)), "kzgx_verify_multi_batch")
+        return bool(ok.value)
+
+    def verify_multi_device(self, d_commits, d_commit_inf, n_commits, d_commit_index, d_group_start, n_groups, d_zs,
+                            d_ys, d_weights, d_proofs, d_proof_inf, d_challenges, count, d_ok, powers=False,
+                            checked=False, subgroup=0, stream=None):
+        """kzgx_verify_multi_batch(_checked)_device: device pointers, d_ok one uint32, enqueued on stream."""
+        args = [self.h, d_commits, d_commit_inf, n_commits, d_commit_index, d_group_start, n_groups, d_zs, d_ys,
+                d_weights, d_proofs, d_proof_inf, d_challenges, count, MULTI_WEIGHT_POWERS if powers else 0]
+        if checked:
+            _chk(lib().kzgx_verify_multi_batch_checked_device(*args, int(bool(subgroup)), d_ok, stream),
+                 "kzgx_verify_multi_batch_checked_device")
+        else:
+            _chk(lib().kzgx_verify_multi_batch_device(*args, d_ok, stream), "kzgx_verify_multi_batch_device")
+
+    def set_multi_chunk(self, scalars: int) -> None:
+        """test knob: scalars of folded polynomials per internal chunk of prove_multi (0 = the default)"""
+        _chk(lib().kzgx_set_multi_chunk(self.h, scalars), "kzgx_set_multi_chunk")
 
     # ---- evaluation form: Fr NTT, commits and openings from evaluations ----
     def ntt(self, a, inverse: bool = False, bitrev: bool = False) -> np.ndarray:

@@ -20,6 +20,7 @@
 
 #include <array>
 #include <cstdint>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -192,6 +193,19 @@ struct batch_opening {
   std::vector<uint32_t> polys;
 };
 
+/** Extension: one opening set of a Shplonk opening (trusted_setup::create_shplonk_proof):
+ *  `points` are indices into the call's list of points (no index twice),
+ *  `polys` indices into its list of polynomials (or, for the verifier,
+ *  commitments); every named polynomial is opened at every named point. */
+struct shplonk_set {
+  std::vector<uint32_t> points, polys;
+};
+
+/** Extension: a Shplonk proof -- two G1 points, whatever was opened. */
+struct shplonk_proof {
+  proof W, Wp;
+};
+
 class trusted_setup {
  private:
   kzgx_ctx* ctx = nullptr;  // device SRS + stream + workspaces
@@ -205,6 +219,10 @@ class trusted_setup {
                         const std::vector<uint32_t>& cell_index, std::vector<proof>& proofs,
                         const std::vector<std::vector<Fr>>& values, unsigned log2n, bool extended, bool bit_reversed,
                         bool checked, bool check_subgroup, std::vector<bool>* each = nullptr);
+  bool shplonk_verified(std::vector<commit>& commits, const std::vector<Fr>& points,
+                        const std::vector<shplonk_set>& sets, const Fr& gamma,
+                        const std::vector<std::vector<Fr>>& values, const Fr& z, shplonk_proof& proof, bool checked,
+                        bool check_subgroup);
   std::vector<Fr> recovered(const std::vector<uint32_t>& cell_index, const std::vector<std::vector<Fr>>& values,
                             unsigned log2n, bool bit_reversed, std::vector<proof>* proofs);
   bool batch_verified(std::vector<commit>& commits, const std::vector<batch_opening>& groups,
@@ -488,6 +506,35 @@ class trusted_setup {
   bool verify_batch_proofs(std::vector<commit>& commits, const std::vector<batch_opening>& groups,
                            const std::vector<Fr>& gammas, const std::vector<std::vector<Fr>>& values,
                            std::vector<proof>& proofs, bool check_subgroup);
+  /** Extension: Shplonk openings (kzgx_shplonk_commit, kzgx_shplonk_open with
+   *  KZGX_SHPLONK_WEIGHT_POWERS): different polynomials opened at different
+   *  point sets under ONE proof of two G1 points.  Claim k, counted over the
+   *  sets in order, has the weight gamma^k.  `challenge` is called once, with
+   *  W, between the two steps and returns z: it must hash W (and what gamma
+   *  hashed), nothing is hashed here.  values_out (optional) receives, set by
+   *  set, every named polynomial's values at the set's points: polynomial j
+   *  of the set's list at [j * points.size(), (j + 1) * points.size()).
+   *  @throws std::invalid_argument on an index beyond `polys` or `points`, an
+   *          index twice in one set, an empty point list or a degree beyond
+   *          the setup; std::domain_error on equal point values in one set */
+  shplonk_proof create_shplonk_proof(const std::vector<kzg::poly>& polys, const std::vector<Fr>& points,
+                                     const std::vector<shplonk_set>& sets, const Fr& gamma,
+                                     const std::function<Fr(const proof&)>& challenge,
+                                     std::vector<std::vector<Fr>>* values_out = nullptr);
+  /** Extension: the verifier's side (kzgx_shplonk_verify): `values` as
+   *  values_out above, z the challenge.  Two variable-base MSMs and ONE
+   *  pairing check.  The second form runs the G1 check of every commitment and
+   *  of both proof points first (check_subgroup: also prime-order membership)
+   *  and is false when one fails.
+   *  @throws std::invalid_argument on mismatched sizes or a malformed table,
+   *          as above */
+  bool verify_shplonk_proof(std::vector<commit>& commits, const std::vector<Fr>& points,
+                            const std::vector<shplonk_set>& sets, const Fr& gamma,
+                            const std::vector<std::vector<Fr>>& values, const Fr& z, shplonk_proof& proof);
+  bool verify_shplonk_proof(std::vector<commit>& commits, const std::vector<Fr>& points,
+                            const std::vector<shplonk_set>& sets, const Fr& gamma,
+                            const std::vector<std::vector<Fr>>& values, const Fr& z, shplonk_proof& proof,
+                            bool check_subgroup);
   /** copy of the G1 / G2 SRS points */
   std::vector<G1> g1_points() const;
   std::vector<G2> g2_points() const;

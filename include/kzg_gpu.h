@@ -33,7 +33,9 @@
  * evaluation-form polynomial at any point, and blob-level prove / verify on 32-byte
  * big-endian scalars and compressed points;
  * kzgx_prove_multi_batch*, kzgx_verify_multi_batch*: batch openings -- many polynomials
- * opened at shared points with one proof per point (both curves).
+ * opened at shared points with one proof per point (both curves);
+ * kzgx_shplonk_commit*, kzgx_shplonk_open*, kzgx_shplonk_verify*: Shplonk openings -- many
+ * polynomials opened at different point sets under one proof of two G1 points (both curves).
  *
  * Conventions
  *   - plain pointers and sizes only; no torch / HIP types in signatures
@@ -1245,10 +1247,10 @@ int kzgx_srs_verify_update(kzgx_ctx* ctx, const uint64_t* prev_tau_g1_xy, const 
  *  128-bit values a false claim passes with probability <= (claims per group + 1) / 2^128.
  *  Points are taken as canonical and on the curve.  Subgroup membership is not checked here
  *  on BLS12-381: that is the _checked forms' business, as for kzgx_verify_aggregate.
- * Out of scope: openings of different polynomials at different point sets under one proof
- *  (BDFG20, "Shplonk"); evaluation-form input (run kzgx_ntt_device first); any hashing of
+ * Out of scope: evaluation-form input (run kzgx_ntt_device first); any hashing of
  *  transcripts; per-group verdicts (fold the commitments with kzgx_msm_g1_points and use
- *  kzgx_verify_single_batch). */
+ *  kzgx_verify_single_batch).  Openings of different polynomials at different point sets
+ *  under one proof are the Shplonk entries below. */
 #define KZGX_MULTI_WEIGHT_POWERS 1 /* weights: one gamma_g per group, w_k = gamma_g^(k - group_start[g]) */
 #define KZGX_MULTI_CHUNK_SCALARS 2097152 /* scalars of folded polynomials per internal chunk */
 #define KZGX_MULTI_EVAL_SLICE 4096 /* coefficients per workgroup of the sliced evaluation */
@@ -1283,6 +1285,159 @@ int kzgx_verify_multi_batch_checked_device(kzgx_ctx* ctx, const void* d_commits,
                                            void* d_ok, void* stream);
 /* test knob: scalars per internal chunk of the prove pipeline (0 restores KZGX_MULTI_CHUNK_SCALARS) */
 int kzgx_set_multi_chunk(kzgx_ctx* ctx, size_t scalars);
+
+/* ---- Shplonk openings: many polynomials at different point sets, one two-point proof (extensions) ----
+ * A proof system opens different polynomials at different point sets -- most at z, some at
+ * z and z w, a few at z, z w and z / w -- and wants one constant-size proof for the whole
+ * table.  This is the scheme of BDFG20 section 4 ("Shplonk"): the proof is two G1 points
+ * (W, W'), whatever the table holds, and the verifier pays two variable-base MSMs and one
+ * two-pairing product.  Needs no evaluation domain and serves both curves.  No reference
+ * counterpart.
+ *
+ * Definitions.
+ *  - Polynomials as for the batch openings: n_polys rows of n >= 1 canonical coefficients,
+ *    row j at coeffs + j * coeff_stride.
+ *  - T: n_points canonical scalars t_0, t_1, ... (points).  Entries of T are told apart BY
+ *    INDEX: the same value may sit at two indices, and two sets naming them are unrelated.
+ *  - n_sets opening sets.  Set s names the d_s >= 1 entries
+ *    set_points[set_point_start[s] .. set_point_start[s+1]) of T (uint32 indices, no index
+ *    twice in one set, d_s <= KZGX_SHPLONK_SET_MAX) and the m_s >= 0 claims
+ *    k in [claim_start[s], claim_start[s+1]).  Both start arrays have n_sets + 1 uint32
+ *    entries, are non-decreasing and run from 0 to n_set_points and to count.
+ *  - Claim k names polynomial poly_index[k] (prover) or commitment commit_index[k] (verifier)
+ *    and has the weight w_k: one canonical scalar per claim, or, with the flag
+ *    KZGX_SHPLONK_WEIGHT_POWERS, weights is ONE scalar gamma and w_k = gamma^k over the
+ *    global claim index k.
+ *  - Values.  y_(k,i) = P_(poly_index[k])(t_i) for the points of the claim's set, laid out
+ *    claim by claim: claim k of set s holds its d_s values, in the set's point order, at
+ *    v_s + (k - claim_start[s]) d_s with v_s = sum_(s' < s) d_s' m_s'.  n_values must be
+ *    sum_s d_s m_s.
+ *  - Z_s = prod_(i in S_s)(X - t_i), F_s = sum_(k in s) w_k P_k, r_k the interpolant of P_k
+ *    on S_s, zeta_s = prod_(i in T \ S_s)(z - t_i), Z_T(z) = prod_(i in T)(z - t_i).
+ *  - Step 1 (kzgx_shplonk_commit): h = sum_s (F_s - R_s) / Z_s = sum_s (F_s div Z_s), n
+ *    scalars with h[n-1] = 0, and W = [h(tau)]G1.  Also the values y.
+ *  - Step 2 (kzgx_shplonk_open), for a challenge z the caller derives AFTER seeing W:
+ *    G = sum_k zeta_(s(k)) w_k P_k - Z_T(z) h and W' = [(G - G(z)) / (X - z)]G1.  W' is bit
+ *    for bit what kzgx_prove_single_batch returns for the polynomial G at z, and the value
+ *    it returns, G(z), equals t below for a correct h.
+ *  - Verifier.  l_(s,i)(z) = c_(s,i) prod_(j in S_s, j != i)(z - t_j) with
+ *    c_(s,i) = 1 / prod_(j != i)(t_i - t_j); r_k(z) = sum_i y_(k,i) l_(s,i)(z);
+ *    s_c = sum_(k : commit_index[k] = c) zeta_(s(k)) w_k; t = sum_k zeta_(s(k)) w_k r_k(z);
+ *     *ok = e(W', G2[1]) == e(sum_c s_c C_c - [t] G1[0] - Z_T(z) W + z W', G2[0]).
+ *    Cost: two variable-base MSMs (1 point; n_commits + 3 points) and one two-pairing
+ *    product, whatever T, the sets and the claims are.
+ *  Everything is in product form, with no division by (z - t_i): z in T is allowed, and
+ *  the answer is then still the equation, though no longer sound.  Two equal VALUES inside
+ *  one set make c_(s,i) undefined: KZGX_ERR_DIV_ZERO on the host, *d_ok = 0 on the device.
+ *  Equal values at different indices in different sets are fine.
+ *
+ * Commit.  out_xy / out_is_inf: W.  out_h: the n scalars of h (step 2 takes them back).
+ *  out_y (may be NULL): the n_values values.  h comes from a fused multi-point quotient:
+ *  F div Z_s = sum_(i in S_s) c_(s,i) (F - F(t_i)) / (X - t_i), so h is a weighted sum of
+ *  independent single-point quotients; field sums run in a fixed order without atomics, so
+ *  the result is bit-reproducible.  The sets are walked in chunks of
+ *  max(1, KZGX_SHPLONK_CHUNK_SCALARS / n) (kzgx_set_shplonk_chunk changes the figure):
+ *  the batch openings' fold kernel writes a chunk's F_s into workspace and the quotient
+ *  kernels add the chunk's share to h.  Up to KZGX_SHPLONK_TILE coefficients the quotient is
+ *  one launch per chunk; above, two more launches carry sums across the tiles.  Workspace per
+ *  stream is bounded by the chunk (max(chunk, n) scalars for F, at most n / 16 + 128 per
+ *  set of the chunk for the carries), plus one scalar per (set, point) pair and, for the
+ *  values, about two per value.  The values come from the batch openings' evaluation kernel
+ *  over the (claim, point) list.
+ * Open.  The same table, h (n scalars) and z; out_xy / out_is_inf: W'; out_Gz (may be
+ *  NULL): G(z).  One fold of all claims under the weights zeta_(s(k)) w_k, one axpy, then
+ *  the unchanged kzgx_prove_single_batch_device.
+ * Verify.  commits: n_commits canonical affine points; ys: the n_values values;
+ *  proof_xy: W then W' (2 points), proof_inf: their 2 flags (may be NULL).  The _checked
+ *  forms run the kzgx_g1_check_batch test over the commitments, W and W' first and force
+ *  *ok = 0 when a point fails, with the same subgroup argument as
+ *  kzgx_verify_multi_batch_checked.
+ *
+ * Host entries validate and return KZGX_ERR_ARG before any device work for: a NULL required
+ *  pointer, n == 0, coeff_stride < n, an unknown flag bit, n_sets == 0 or >= 2^16, a start
+ *  array that does not run non-decreasing from 0 to its total, d_s == 0 or
+ *  > KZGX_SHPLONK_SET_MAX, n_points == 0 or > KZGX_SHPLONK_POINTS_MAX, an index out of range,
+ *  the same index twice in one set, a scalar >= r, n_values != sum_s d_s m_s, count >= 2^31.
+ *  Then: equal values in one set: KZGX_ERR_DIV_ZERO; no SRS: KZGX_ERR_NO_SRS (the verify
+ *  needs G1[0] and G2[0..1] only); n - 1 larger than the SRS on the prove side:
+ *  KZGX_ERR_DEGREE.
+ * Device entries are asynchronous on stream (NULL = the context's) and read nothing back
+ *  (n == 1 excepted, as for the batch openings).  They check what the host can see
+ *  (pointers, sizes, flags; n_values < 2^31).  Whatever the index arrays hold, nothing is
+ *  read or written out of bounds: start ranges are clamped to their totals and a set to its
+ *  first KZGX_SHPLONK_SET_MAX points, a point index >= n_points is skipped, a claim naming a
+ *  polynomial or commitment out of range contributes nothing and its values are 0, values
+ *  past n_values are neither written nor read.  Any such input, a repeated index or equal
+ *  values in one set, or a wrong n_values forces *d_ok = 0 (one uint32; it may be NULL on
+ *  the commit and open side, where it reports only this validation; the open side does not
+ *  need c_(s,i) and does not look for equal values).  With *d_ok = 0 the outputs are
+ *  defined but meaningless.
+ *
+ * Soundness.  The library hashes nothing.  With explicit weights and z the answer is a
+ *  deterministic function of the inputs: the equation above and nothing else.  An honest
+ *  proof passes.  gamma must come from a transcript that binds the commitments, T, the sets
+ *  and the claimed values; z must bind W as well -- that is why there are two prover
+ *  entries and not one: a prover that knows z before it fixes W can make a false claim
+ *  pass.  With unpredictable values a false claim passes with probability about
+ *  (count + n) / r.  Points are taken as canonical and on the curve; subgroup membership is
+ *  the _checked forms' business.
+ * Out of scope: transcript hashing; batching several Shplonk proofs into one check;
+ *  evaluation-form input (run kzgx_ntt_device first); a command-line verb. */
+#define KZGX_SHPLONK_WEIGHT_POWERS 1 /* weights: one gamma, w_k = gamma^k over the global claim index */
+#define KZGX_SHPLONK_SET_MAX 64 /* points per opening set */
+#define KZGX_SHPLONK_POINTS_MAX 4096 /* entries of T */
+#define KZGX_SHPLONK_CHUNK_SCALARS 2097152 /* scalars of folded polynomials per internal chunk */
+#define KZGX_SHPLONK_TILE 2048 /* coefficients per workgroup of the fused quotient: above, carries cross tiles */
+int kzgx_shplonk_commit(kzgx_ctx* ctx, const uint64_t* coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                        const uint64_t* points, size_t n_points, const uint32_t* set_point_start,
+                        const uint32_t* set_points, size_t n_set_points, const uint32_t* claim_start,
+                        const uint32_t* poly_index, size_t n_sets, const uint64_t* weights, size_t count,
+                        size_t n_values, int flags, uint64_t* out_xy, int* out_is_inf, uint64_t* out_h,
+                        uint64_t* out_y);
+int kzgx_shplonk_commit_device(kzgx_ctx* ctx, const void* d_coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                               const void* d_points, size_t n_points, const void* d_set_point_start,
+                               const void* d_set_points, size_t n_set_points, const void* d_claim_start,
+                               const void* d_poly_index, size_t n_sets, const void* d_weights, size_t count,
+                               size_t n_values, int flags, void* d_out_xy, void* d_out_is_inf, void* d_out_h,
+                               void* d_out_y, void* d_ok, void* stream);
+int kzgx_shplonk_open(kzgx_ctx* ctx, const uint64_t* coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                      const uint64_t* points, size_t n_points, const uint32_t* set_point_start,
+                      const uint32_t* set_points, size_t n_set_points, const uint32_t* claim_start,
+                      const uint32_t* poly_index, size_t n_sets, const uint64_t* weights, size_t count, int flags,
+                      const uint64_t* h, const uint64_t* z, uint64_t* out_xy, int* out_is_inf, uint64_t* out_Gz);
+int kzgx_shplonk_open_device(kzgx_ctx* ctx, const void* d_coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                             const void* d_points, size_t n_points, const void* d_set_point_start,
+                             const void* d_set_points, size_t n_set_points, const void* d_claim_start,
+                             const void* d_poly_index, size_t n_sets, const void* d_weights, size_t count, int flags,
+                             const void* d_h, const void* d_z, void* d_out_xy, void* d_out_is_inf, void* d_out_Gz,
+                             void* d_ok, void* stream);
+int kzgx_shplonk_verify(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                        const uint32_t* commit_index, const uint64_t* points, size_t n_points,
+                        const uint32_t* set_point_start, const uint32_t* set_points, size_t n_set_points,
+                        const uint32_t* claim_start, size_t n_sets, const uint64_t* ys, size_t n_values,
+                        const uint64_t* weights, size_t count, const uint64_t* z, const uint64_t* proof_xy,
+                        const int* proof_inf, int flags, int* ok);
+int kzgx_shplonk_verify_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, size_t n_commits,
+                               const void* d_commit_index, const void* d_points, size_t n_points,
+                               const void* d_set_point_start, const void* d_set_points, size_t n_set_points,
+                               const void* d_claim_start, size_t n_sets, const void* d_ys, size_t n_values,
+                               const void* d_weights, size_t count, const void* d_z, const void* d_proof_xy,
+                               const void* d_proof_inf, int flags, void* d_ok, void* stream);
+int kzgx_shplonk_verify_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                                const uint32_t* commit_index, const uint64_t* points, size_t n_points,
+                                const uint32_t* set_point_start, const uint32_t* set_points, size_t n_set_points,
+                                const uint32_t* claim_start, size_t n_sets, const uint64_t* ys, size_t n_values,
+                                const uint64_t* weights, size_t count, const uint64_t* z, const uint64_t* proof_xy,
+                                const int* proof_inf, int flags, int subgroup, int* ok);
+int kzgx_shplonk_verify_checked_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                       size_t n_commits, const void* d_commit_index, const void* d_points,
+                                       size_t n_points, const void* d_set_point_start, const void* d_set_points,
+                                       size_t n_set_points, const void* d_claim_start, size_t n_sets,
+                                       const void* d_ys, size_t n_values, const void* d_weights, size_t count,
+                                       const void* d_z, const void* d_proof_xy, const void* d_proof_inf, int flags,
+                                       int subgroup, void* d_ok, void* stream);
+/* test knob: scalars per internal chunk of the commit pipeline (0 restores KZGX_SHPLONK_CHUNK_SCALARS) */
+int kzgx_set_shplonk_chunk(kzgx_ctx* ctx, size_t scalars);
 
 #ifdef __cplusplus
 }

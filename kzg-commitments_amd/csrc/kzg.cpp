@@ -1394,6 +1394,152 @@ bool trusted_setup::batch_verified(std::vector<commit>& commits, const std::vect
   return ok != 0;
 }
 
+namespace {
+// sets -> the C ABI's flat table: point indices and claim indices set by set, with their start arrays
+struct shplonk_table {
+  std::vector<uint32_t> sps, sp, cs, index;
+  std::vector<uint64_t> t;
+  size_t n_values = 0;
+};
+
+shplonk_table flatten_sets(const std::vector<Fr>& points, const std::vector<shplonk_set>& sets, size_t n_index,
+                           const char* who) {
+  if (sets.empty() || points.empty()) throw std::invalid_argument(std::string(who) + ": no sets or no points");
+  shplonk_table c;
+  c.sps.push_back(0);
+  c.cs.push_back(0);
+  for (auto& s : sets) {
+    if (s.points.empty() || s.points.size() > KZGX_SHPLONK_SET_MAX)
+      throw std::invalid_argument(std::string(who) + ": 1 .. KZGX_SHPLONK_SET_MAX points per set");
+    for (size_t a = 0; a < s.points.size(); a++) {
+      if (s.points[a] >= points.size()) throw std::invalid_argument(std::string(who) + ": point index out of range");
+      for (size_t b = 0; b < a; b++)
+        if (s.points[a] == s.points[b]) throw std::invalid_argument(std::string(who) + ": an index twice in one set");
+      c.sp.push_back(s.points[a]);
+    }
+    for (uint32_t j : s.polys) {
+      if (j >= n_index) throw std::invalid_argument(std::string(who) + ": index out of range");
+      c.index.push_back(j);
+    }
+    c.sps.push_back((uint32_t)c.sp.size());
+    c.cs.push_back((uint32_t)c.index.size());
+    c.n_values += s.points.size() * s.polys.size();
+  }
+  for (auto& p : points) c.t.insert(c.t.end(), p.v.begin(), p.v.end());
+  c.index.push_back(0);  // never NULL
+  return c;
+}
+}  // namespace
+
+shplonk_proof trusted_setup::create_shplonk_proof(const std::vector<kzg::poly>& polys, const std::vector<Fr>& points,
+                                                  const std::vector<shplonk_set>& sets, const Fr& gamma,
+                                                  const std::function<Fr(const proof&)>& challenge,
+                                                  std::vector<std::vector<Fr>>* values_out) {
+  shplonk_table tb = flatten_sets(points, sets, polys.size(), "create_shplonk_proof");
+  if (!challenge) throw std::invalid_argument("create_shplonk_proof: no challenge function");
+  size_t m = 1;  // zero-padded to a common length (the zero polynomial: one zero coefficient)
+  for (auto& p : polys) m = std::max(m, p.get_poly().size());
+  if (m - 1 > n) throw std::invalid_argument("polynomial degree be at most one less than the setup size (num_coeffs)");
+  std::vector<uint64_t> s(4 * m * std::max<size_t>(polys.size(), 1), 0);
+  for (size_t b = 0; b < polys.size(); b++) {
+    auto f = flat(polys[b].get_poly());
+    if (!f.empty()) std::memcpy(&s[4 * m * b], f.data(), f.size() * 8);
+  }
+  const int nl = base_limbs();
+  const size_t count = tb.index.size() - 1;
+  std::vector<uint64_t> out(2 * nl), h(4 * m), y(4 * tb.n_values + 4);
+  int inf = 0;
+  check(kzgx_shplonk_commit(ctx, s.data(), m, m, polys.size(), tb.t.data(), points.size(), tb.sps.data(),
+                            tb.sp.data(), tb.sp.size(), tb.cs.data(), tb.index.data(), sets.size(), gamma.v.data(),
+                            count, tb.n_values, KZGX_SHPLONK_WEIGHT_POWERS, out.data(), &inf, h.data(),
+                            values_out ? y.data() : nullptr),
+        "kzgx_shplonk_commit");
+  shplonk_proof res{proof(to_g1(out.data(), inf)), proof(to_g1(out.data(), 1))};
+  const Fr z = challenge(res.W);
+  check(kzgx_shplonk_open(ctx, s.data(), m, m, polys.size(), tb.t.data(), points.size(), tb.sps.data(), tb.sp.data(),
+                          tb.sp.size(), tb.cs.data(), tb.index.data(), sets.size(), gamma.v.data(), count,
+                          KZGX_SHPLONK_WEIGHT_POWERS, h.data(), z.v.data(), out.data(), &inf, nullptr),
+        "kzgx_shplonk_open");
+  res.Wp = proof(to_g1(out.data(), inf));
+  if (values_out) {
+    values_out->clear();
+    size_t v = 0;
+    for (auto& st : sets) {
+      std::vector<Fr> vals(st.points.size() * st.polys.size());
+      for (auto& f : vals) {
+        std::memcpy(f.v.data(), &y[4 * v], 32);
+        v++;
+      }
+      values_out->push_back(std::move(vals));
+    }
+  }
+  return res;
+}
+
+bool trusted_setup::verify_shplonk_proof(std::vector<commit>& commits, const std::vector<Fr>& points,
+                                         const std::vector<shplonk_set>& sets, const Fr& gamma,
+                                         const std::vector<std::vector<Fr>>& values, const Fr& z,
+                                         shplonk_proof& proof) {
+  return shplonk_verified(commits, points, sets, gamma, values, z, proof, false, false);
+}
+
+bool trusted_setup::verify_shplonk_proof(std::vector<commit>& commits, const std::vector<Fr>& points,
+                                         const std::vector<shplonk_set>& sets, const Fr& gamma,
+                                         const std::vector<std::vector<Fr>>& values, const Fr& z,
+                                         shplonk_proof& proof, bool check_subgroup) {
+  return shplonk_verified(commits, points, sets, gamma, values, z, proof, true, check_subgroup);
+}
+
+bool trusted_setup::shplonk_verified(std::vector<commit>& commits, const std::vector<Fr>& points,
+                                     const std::vector<shplonk_set>& sets, const Fr& gamma,
+                                     const std::vector<std::vector<Fr>>& values, const Fr& z, shplonk_proof& pr,
+                                     bool checked, bool check_subgroup) {
+  shplonk_table tb = flatten_sets(points, sets, commits.size(), "verify_shplonk_proof");
+  if (values.size() != sets.size()) throw std::invalid_argument("verify_shplonk_proof: size mismatch");
+  std::vector<uint64_t> y;
+  for (size_t s = 0; s < sets.size(); s++) {
+    if (values[s].size() != sets[s].points.size() * sets[s].polys.size())
+      throw std::invalid_argument("verify_shplonk_proof: one value per opened commitment and point");
+    for (auto& v : values[s]) y.insert(y.end(), v.v.begin(), v.v.end());
+  }
+  y.resize(y.size() + 4);
+  const int nl = base_limbs();
+  const size_t nc = commits.size(), count = tb.index.size() - 1;
+  std::vector<uint64_t> c(2 * nl * nc + 1, 0), p(4 * nl, 0);
+  std::vector<int> ci(nc + 1), pi(2);
+  for (size_t k = 0; k < nc; k++) {
+    const G1& cg = commits[k].get_curve_point();
+    for (int i = 0; i < nl; i++) {
+      c[2 * nl * k + i] = cg.x[i];
+      c[2 * nl * k + nl + i] = cg.y[i];
+    }
+    ci[k] = cg.inf;
+  }
+  proof* both[2] = {&pr.W, &pr.Wp};
+  for (int g = 0; g < 2; g++) {
+    const G1& pg = both[g]->get_curve_point();
+    for (int i = 0; i < nl; i++) {
+      p[2 * nl * g + i] = pg.x[i];
+      p[2 * nl * g + nl + i] = pg.y[i];
+    }
+    pi[g] = pg.inf;
+  }
+  int ok = 0;
+  if (checked)
+    check(kzgx_shplonk_verify_checked(ctx, c.data(), ci.data(), nc, tb.index.data(), tb.t.data(), points.size(),
+                                      tb.sps.data(), tb.sp.data(), tb.sp.size(), tb.cs.data(), sets.size(), y.data(),
+                                      tb.n_values, gamma.v.data(), count, z.v.data(), p.data(), pi.data(),
+                                      KZGX_SHPLONK_WEIGHT_POWERS, check_subgroup ? 1 : 0, &ok),
+          "kzgx_shplonk_verify_checked");
+  else
+    check(kzgx_shplonk_verify(ctx, c.data(), ci.data(), nc, tb.index.data(), tb.t.data(), points.size(),
+                              tb.sps.data(), tb.sp.data(), tb.sp.size(), tb.cs.data(), sets.size(), y.data(),
+                              tb.n_values, gamma.v.data(), count, z.v.data(), p.data(), pi.data(),
+                              KZGX_SHPLONK_WEIGHT_POWERS, &ok),
+          "kzgx_shplonk_verify");
+  return ok != 0;
+}
+
 std::vector<G1> trusted_setup::g1_points() const {
   const int nl = base_limbs();
   std::vector<uint64_t> xy(2 * nl * n);

@@ -24,6 +24,7 @@
 #include "kzgx_internal.hpp"
 #include "kzgx_setup.hpp"
 #include "multi_open.hpp"
+#include "shplonk.hpp"
 
 // a generated G2 SRS of at most this many points gets its polyeval_G2 window
 // table at setup (kzgx_gen_srs_g2); larger ones on first use
@@ -68,6 +69,12 @@ struct kzgx_ctx {
   uint32_t* d_multi[kzgx::KZGX_MAX_STREAMS] = {};
   size_t multi_b[kzgx::KZGX_MAX_STREAMS] = {};
   size_t multi_chunk = 0;
+  // the Shplonk openings' buffers (pair constants, a chunk's folded polynomials and tile carries, the
+  // value list, the verifier's scalars), per slot as d_chk; shplonk_chunk: scalars per chunk
+  // (0 = KZGX_SHPLONK_CHUNK_SCALARS)
+  uint32_t* d_shp[kzgx::KZGX_MAX_STREAMS] = {};
+  size_t shp_b[kzgx::KZGX_MAX_STREAMS] = {};
+  size_t shplonk_chunk = 0;
 
   // pinned, device-mapped host staging for the host-pointer entry points
   // (kzgx_msm_g1_batch, kzgx_prove_single_batch): inputs are copied into it
@@ -634,6 +641,8 @@ void kzgx_destroy(kzgx_ctx* ctx) {
   for (void* p : ctx->d_blob)
     if (p) (void)hipFree(p);
   for (void* p : ctx->d_multi)
+    if (p) (void)hipFree(p);
+  for (void* p : ctx->d_shp)
     if (p) (void)hipFree(p);
   for (auto& f : c.fk) {
     if (f.x) (void)hipFree(f.x);
@@ -3983,6 +3992,532 @@ int kzgx_verify_multi_batch_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, c
                                     size_t count, int flags, int subgroup, int* ok) {
   return verify_multi_host(ctx, commits_xy, commit_inf, n_commits, commit_index, group_start, n_groups, zs, ys,
                            weights, proofs_xy, proof_inf, challenges, count, flags, true, subgroup, ok);
+}
+
+}  // extern "C"
+
+// ---- Shplonk openings: many polynomials at different point sets, one two-point proof (shplonk.hip) ----
+namespace {
+// the Shplonk buffer of the workspace slot leased for this call's stream, carved front to back
+struct ShpArena {
+  char* p = nullptr;
+  size_t used = 0;
+  template <class T>
+  T* take(size_t bytes) {
+    T* r = (T*)(p + used);
+    used += align32(bytes);
+    return r;
+  }
+};
+int shp_scratch(kzgx_ctx* ctx, const kzgx::WsLease& ws, size_t bytes, ShpArena* a) {
+  const size_t slot = (size_t)(ws.get() - ctx->c.ws);
+  KZGX_TRY(kzgx::dev_alloc(&ctx->c, (void**)&ctx->d_shp[slot], bytes, &ctx->shp_b[slot]));
+  a->p = (char*)ctx->d_shp[slot];
+  a->used = 0;
+  return KZGX_OK;
+}
+
+// what the host can see of a call's shape, both sides (n_index: polynomials or commitments)
+bool shp_shape_ok(size_t n_index, size_t n_points, size_t n_set_points, size_t n_sets, size_t count, size_t n_values,
+                  int flags) {
+  return (flags & ~KZGX_SHPLONK_WEIGHT_POWERS) == 0 && n_index <= 0xffffffffu && n_sets > 0 && n_sets < 65536 &&
+         n_points > 0 && n_points <= KZGX_SHPLONK_POINTS_MAX && n_set_points > 0 &&
+         n_set_points <= n_sets * KZGX_SHPLONK_SET_MAX && count <= 0x7fffffffu && n_values <= 0x7fffffffu;
+}
+
+kzgx::ShpTable shp_table(const void* d_points, size_t n_points, const void* d_sps, const void* d_sp,
+                         size_t n_set_points, const void* d_cs, size_t n_sets, size_t count) {
+  kzgx::ShpTable t;
+  t.points = (const uint32_t*)d_points;
+  t.set_point_start = (const uint32_t*)d_sps;
+  t.set_points = (const uint32_t*)d_sp;
+  t.claim_start = (const uint32_t*)d_cs;
+  t.n_points = (uint32_t)n_points;
+  t.n_set_points = (uint32_t)n_set_points;
+  t.n_sets = (uint32_t)n_sets;
+  t.count = (uint32_t)count;
+  return t;
+}
+
+// the host entries' structure check (KZGX_ERR_ARG), then equal values inside one set (KZGX_ERR_DIV_ZERO).
+// n_values == SIZE_MAX: the call has no values (kzgx_shplonk_open).
+int shp_structure(int curve, const uint32_t* index, size_t n_index, const uint64_t* points, size_t n_points,
+                  const uint32_t* sps, const uint32_t* sp, size_t n_set_points, const uint32_t* cs, size_t n_sets,
+                  size_t count, size_t n_values) {
+  if (sps[0] != 0 || sps[n_sets] != n_set_points || cs[0] != 0 || cs[n_sets] != count) return KZGX_ERR_ARG;
+  uint64_t total = 0;
+  for (size_t s = 0; s < n_sets; s++) {
+    if (sps[s] >= sps[s + 1] || sps[s + 1] - sps[s] > KZGX_SHPLONK_SET_MAX || cs[s] > cs[s + 1]) return KZGX_ERR_ARG;
+    total += (uint64_t)(sps[s + 1] - sps[s]) * (cs[s + 1] - cs[s]);
+  }
+  if (n_values != SIZE_MAX && total != n_values) return KZGX_ERR_ARG;
+  for (size_t j = 0; j < n_set_points; j++)
+    if (sp[j] >= n_points) return KZGX_ERR_ARG;
+  for (size_t k = 0; k < count; k++)
+    if (index[k] >= n_index) return KZGX_ERR_ARG;
+  for (size_t s = 0; s < n_sets; s++)
+    for (uint32_t a = sps[s]; a < sps[s + 1]; a++)
+      for (uint32_t b = a + 1; b < sps[s + 1]; b++)
+        if (sp[a] == sp[b]) return KZGX_ERR_ARG;
+  if (!multi_canonical(curve, points, n_points)) return KZGX_ERR_ARG;
+  for (size_t s = 0; s < n_sets; s++)
+    for (uint32_t a = sps[s]; a < sps[s + 1]; a++)
+      for (uint32_t b = a + 1; b < sps[s + 1]; b++)
+        if (std::memcmp(points + 4 * (size_t)sp[a], points + 4 * (size_t)sp[b], 32) == 0) return KZGX_ERR_DIV_ZERO;
+  return KZGX_OK;
+}
+
+// the index arrays of a host call in one staging block: set_point_start | set_points | claim_start | index
+struct ShpIdx {
+  size_t o_sps, o_sp, o_cs, o_ix, bytes;
+};
+ShpIdx shp_idx_layout(size_t n_set_points, size_t n_sets, size_t count) {
+  ShpIdx l;
+  l.o_sps = 0;
+  l.o_sp = l.o_sps + align32((n_sets + 1) * 4);
+  l.o_cs = l.o_sp + align32(n_set_points * 4);
+  l.o_ix = l.o_cs + align32((n_sets + 1) * 4);
+  l.bytes = l.o_ix + align32(count * 4);
+  return l;
+}
+int shp_idx_copy(char* d, const ShpIdx& l, const uint32_t* sps, const uint32_t* sp, size_t n_set_points,
+                 const uint32_t* cs, const uint32_t* index, size_t n_sets, size_t count, hipStream_t st) {
+  KZGX_TRY_HIP(hipMemcpyAsync(d + l.o_sps, sps, (n_sets + 1) * 4, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d + l.o_sp, sp, n_set_points * 4, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d + l.o_cs, cs, (n_sets + 1) * 4, hipMemcpyHostToDevice, st));
+  if (count) KZGX_TRY_HIP(hipMemcpyAsync(d + l.o_ix, index, count * 4, hipMemcpyHostToDevice, st));
+  return KZGX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kzgx_set_shplonk_chunk(kzgx_ctx* ctx, size_t scalars) {
+  if (!ctx) return KZGX_ERR_ARG;
+  ctx->shplonk_chunk = scalars;
+  return KZGX_OK;
+}
+
+int kzgx_shplonk_commit_device(kzgx_ctx* ctx, const void* d_coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                               const void* d_points, size_t n_points, const void* d_set_point_start,
+                               const void* d_set_points, size_t n_set_points, const void* d_claim_start,
+                               const void* d_poly_index, size_t n_sets, const void* d_weights, size_t count,
+                               size_t n_values, int flags, void* d_out_xy, void* d_out_is_inf, void* d_out_h,
+                               void* d_out_y, void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (!shp_shape_ok(n_polys, n_points, n_set_points, n_sets, count, n_values, flags) || n == 0 || n > 0xffffffffu ||
+      coeff_stride < n)
+    return KZGX_ERR_ARG;
+  if (!d_coeffs || !d_points || !d_set_point_start || !d_set_points || !d_claim_start || !d_weights || !d_out_xy ||
+      !d_out_is_inf || !d_out_h || (count > 0 && !d_poly_index))
+    return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  if (n - 1 > ctx->c.n_srs) return KZGX_ERR_DEGREE;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::Ctx* c = &ctx->c;
+  kzgx::WsLease ws = c->ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const bool powers = (flags & KZGX_SHPLONK_WEIGHT_POWERS) != 0;
+  const size_t chunk = ctx->shplonk_chunk ? ctx->shplonk_chunk : kzgx::SHP_CHUNK_SCALARS;
+  const size_t cs = std::min(std::max<size_t>(1, chunk / n), n_sets);  // sets per chunk (n_sets < 2^16)
+  const size_t NT = kzgx::shp_tiles(n);
+  // the values: as kzgx_prove_multi_batch_device's claims, over the (claim, point) list
+  const uint32_t slice = kzgx::MULTI_EVAL_SLICE;
+  const size_t nsl = n > slice ? (n + slice - 1) / slice : 0;
+  const bool want_y = d_out_y && n_values > 0;
+  const size_t ek = !want_y ? 0 : nsl ? std::min(std::max<size_t>(1, chunk / nsl), n_values) : n_values;
+  const size_t part_sc = want_y ? kzgx::multi_eval_part_scalars(ek, n, slice) : 0;
+  const size_t tot_sc = NT > 1 ? cs * kzgx::SHP_SET_MAX * NT * 2 : 0;
+  ShpArena a;
+  KZGX_TRY(shp_scratch(ctx, ws,
+                       (n_set_points + (powers ? count : 0) + cs * n + tot_sc + (want_y ? n_values + part_sc : 0)) * 32 +
+                           align32((n_sets + 1) * 8) + 32 + (want_y ? 2 * align32((n_values + 1) * 4) : 0) + 8 * 32,
+                       &a));
+  uint32_t* pc = a.take<uint32_t>(n_set_points * 32);
+  uint32_t* wexp = a.take<uint32_t>(powers ? count * 32 : 0);
+  uint32_t* F = a.take<uint32_t>(cs * n * 32);
+  uint32_t* tot = a.take<uint32_t>(tot_sc * 32);
+  uint64_t* voff = a.take<uint64_t>((n_sets + 1) * 8);
+  uint32_t* gate = a.take<uint32_t>(32);
+  const kzgx::ShpTable t =
+      shp_table(d_points, n_points, d_set_point_start, d_set_points, n_set_points, d_claim_start, n_sets, count);
+  const uint32_t* pidx = (const uint32_t*)d_poly_index;
+  KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)gate, 1, 1, st));
+  KZGX_TRY(kzgx::shp_check(t, pidx, n_polys, gate, st));
+  KZGX_TRY(kzgx::shp_pairs(c, t, nullptr, pc, nullptr, gate, st));
+  KZGX_TRY(kzgx::shp_offsets(t, voff, n_values, gate, st));
+  const uint32_t* wts = (const uint32_t*)d_weights;
+  if (powers) {
+    KZGX_TRY(kzgx::shp_weight_powers(c, wts, count, wexp, st));
+    wts = wexp;
+  }
+  for (size_t s0 = 0; s0 < n_sets; s0 += cs) {
+    const size_t ns = std::min(cs, n_sets - s0);
+    KZGX_TRY(kzgx::multi_fold(c, (const uint32_t*)d_coeffs, n, coeff_stride * 8, n_polys, pidx, t.claim_start, s0, ns,
+                              count, wts, false, F, st));
+    KZGX_TRY(kzgx::shp_quotient(c, t, F, n, s0, ns, pc, tot, (uint32_t*)d_out_h, s0 > 0, st));
+  }
+  // W = [h(tau)]G1 over the n - 1 scalars that can be non-zero
+  KZGX_TRY(kzgx_msm_g1_batch_device(ctx, d_out_h, n - 1, 1, n - 1, d_out_xy, d_out_is_inf, st));
+  if (want_y) {
+    uint32_t* ezs = a.take<uint32_t>(n_values * 32);
+    uint32_t* part = a.take<uint32_t>(part_sc * 32);
+    uint32_t* epoly = a.take<uint32_t>((n_values + 1) * 4);
+    uint32_t* egs = a.take<uint32_t>((n_values + 1) * 4);
+    KZGX_TRY(kzgx::shp_expand(c, t, voff, pidx, n_values, epoly, ezs, egs, st));
+    for (size_t k0 = 0; k0 < n_values; k0 += ek)
+      KZGX_TRY(kzgx::multi_eval(c, (const uint32_t*)d_coeffs, n, coeff_stride * 8, n_polys, epoly, egs, n_values, ezs,
+                                k0, std::min(ek, n_values - k0), (uint32_t*)d_out_y, part, slice, st));
+  }
+  if (d_ok) KZGX_TRY_HIP(hipMemcpyAsync(d_ok, gate, 4, hipMemcpyDeviceToDevice, st));
+  return KZGX_OK;
+}
+
+int kzgx_shplonk_commit(kzgx_ctx* ctx, const uint64_t* coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                        const uint64_t* points, size_t n_points, const uint32_t* set_point_start,
+                        const uint32_t* set_points, size_t n_set_points, const uint32_t* claim_start,
+                        const uint32_t* poly_index, size_t n_sets, const uint64_t* weights, size_t count,
+                        size_t n_values, int flags, uint64_t* out_xy, int* out_is_inf, uint64_t* out_h,
+                        uint64_t* out_y) {
+  KZGX_TRY(activate(ctx));
+  if (!shp_shape_ok(n_polys, n_points, n_set_points, n_sets, count, n_values, flags) || n == 0 || n > 0xffffffffu ||
+      coeff_stride < n)
+    return KZGX_ERR_ARG;
+  if (!points || !set_point_start || !set_points || !claim_start || !weights || !out_xy || !out_is_inf || !out_h ||
+      (count > 0 && !poly_index) || (n_polys > 0 && !coeffs))
+    return KZGX_ERR_ARG;
+  const size_t nw = (flags & KZGX_SHPLONK_WEIGHT_POWERS) ? 1 : count;
+  if (!multi_canonical(ctx->c.curve, weights, nw)) return KZGX_ERR_ARG;
+  KZGX_TRY(shp_structure(ctx->c.curve, poly_index, n_polys, points, n_points, set_point_start, set_points,
+                         n_set_points, claim_start, n_sets, count, n_values));
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  if (n - 1 > ctx->c.n_srs) return KZGX_ERR_DEGREE;
+  const size_t pb = point_words(ctx) * 4;
+  const size_t cb = n_polys ? ((n_polys - 1) * coeff_stride + n) * 32 : 32;
+  // inputs: points | weights | index arrays; outputs: W | flag | h | y
+  const ShpIdx il = shp_idx_layout(n_set_points, n_sets, count);
+  const size_t i_w = n_points * 32, i_x = i_w + std::max<size_t>(nw, 1) * 32, i_end = i_x + il.bytes;
+  const size_t o_f = align32(pb), o_h = o_f + 32, o_y = o_h + n * 32, o_end = o_y + std::max<size_t>(n_values, 1) * 32;
+  void *d_c, *d_i, *d_o;
+  KZGX_TRY(stage(ctx, 0, cb, &d_c));
+  KZGX_TRY(stage(ctx, 1, i_end, &d_i));
+  KZGX_TRY(stage(ctx, 2, o_end, &d_o));
+  hipStream_t st = ctx->c.stream;
+  char *in = (char*)d_i, *out = (char*)d_o;
+  if (n_polys) KZGX_TRY_HIP(hipMemcpyAsync(d_c, coeffs, cb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(in, points, n_points * 32, hipMemcpyHostToDevice, st));
+  if (nw) KZGX_TRY_HIP(hipMemcpyAsync(in + i_w, weights, nw * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY(shp_idx_copy(in + i_x, il, set_point_start, set_points, n_set_points, claim_start, poly_index, n_sets, count,
+                        st));
+  KZGX_TRY(kzgx_shplonk_commit_device(ctx, d_c, n, coeff_stride, n_polys, in, n_points, in + i_x + il.o_sps,
+                                      in + i_x + il.o_sp, n_set_points, in + i_x + il.o_cs, in + i_x + il.o_ix, n_sets,
+                                      in + i_w, count, n_values, flags, out, out + o_f, out + o_h,
+                                      out_y ? out + o_y : nullptr, nullptr, nullptr));
+  uint32_t inf = 0;
+  KZGX_TRY_HIP(hipMemcpyAsync(out_xy, out, pb, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(&inf, out + o_f, 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(out_h, out + o_h, n * 32, hipMemcpyDeviceToHost, st));
+  if (out_y && n_values) KZGX_TRY_HIP(hipMemcpyAsync(out_y, out + o_y, n_values * 32, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  *out_is_inf = (int)inf;
+  return KZGX_OK;
+}
+
+int kzgx_shplonk_open_device(kzgx_ctx* ctx, const void* d_coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                             const void* d_points, size_t n_points, const void* d_set_point_start,
+                             const void* d_set_points, size_t n_set_points, const void* d_claim_start,
+                             const void* d_poly_index, size_t n_sets, const void* d_weights, size_t count, int flags,
+                             const void* d_h, const void* d_z, void* d_out_xy, void* d_out_is_inf, void* d_out_Gz,
+                             void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (!shp_shape_ok(n_polys, n_points, n_set_points, n_sets, count, 0, flags) || n == 0 || n > 0xffffffffu ||
+      coeff_stride < n)
+    return KZGX_ERR_ARG;
+  if (!d_coeffs || !d_points || !d_set_point_start || !d_set_points || !d_claim_start || !d_weights || !d_h || !d_z ||
+      !d_out_xy || !d_out_is_inf || (count > 0 && !d_poly_index))
+    return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  if (n - 1 > ctx->c.n_srs) return KZGX_ERR_DEGREE;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::Ctx* c = &ctx->c;
+  kzgx::WsLease ws = c->ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const bool powers = (flags & KZGX_SHPLONK_WEIGHT_POWERS) != 0;
+  ShpArena a;
+  KZGX_TRY(shp_scratch(ctx, ws, (n_sets + 1 + (powers ? count : 0) + count + n) * 32 + 2 * 32 + 8 * 32, &a));
+  uint32_t* zeta = a.take<uint32_t>((n_sets + 1) * 32);
+  uint32_t* wexp = a.take<uint32_t>(powers ? count * 32 : 0);
+  uint32_t* cw = a.take<uint32_t>(count * 32);
+  uint32_t* G = a.take<uint32_t>(n * 32);
+  uint32_t* gs2 = a.take<uint32_t>(32);
+  uint32_t* gate = a.take<uint32_t>(32);
+  const kzgx::ShpTable t =
+      shp_table(d_points, n_points, d_set_point_start, d_set_points, n_set_points, d_claim_start, n_sets, count);
+  const uint32_t* pidx = (const uint32_t*)d_poly_index;
+  KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)gate, 1, 1, st));
+  KZGX_TRY(kzgx::shp_check(t, pidx, n_polys, gate, st));
+  KZGX_TRY(kzgx::shp_zeta(c, t, (const uint32_t*)d_z, zeta, st));
+  const uint32_t* wts = (const uint32_t*)d_weights;
+  if (powers) {
+    KZGX_TRY(kzgx::shp_weight_powers(c, wts, count, wexp, st));
+    wts = wexp;
+  }
+  // G = sum_k zeta_(s(k)) w_k P_k - Z_T(z) h: one fold of all claims as one group, one axpy
+  KZGX_TRY(kzgx::shp_claim_weights(c, t, zeta, wts, cw, gs2, st));
+  KZGX_TRY(kzgx::multi_fold(c, (const uint32_t*)d_coeffs, n, coeff_stride * 8, n_polys, pidx, gs2, 0, 1, count, cw,
+                            false, G, st));
+  KZGX_TRY(kzgx::shp_axpy(c, G, (const uint32_t*)d_h, zeta + n_sets * 8, n, st));
+  KZGX_TRY(kzgx_prove_single_batch_device(ctx, G, n, n, d_z, 1, d_out_xy, d_out_is_inf, d_out_Gz, st));
+  if (d_ok) KZGX_TRY_HIP(hipMemcpyAsync(d_ok, gate, 4, hipMemcpyDeviceToDevice, st));
+  return KZGX_OK;
+}
+
+int kzgx_shplonk_open(kzgx_ctx* ctx, const uint64_t* coeffs, size_t n, size_t coeff_stride, size_t n_polys,
+                      const uint64_t* points, size_t n_points, const uint32_t* set_point_start,
+                      const uint32_t* set_points, size_t n_set_points, const uint32_t* claim_start,
+                      const uint32_t* poly_index, size_t n_sets, const uint64_t* weights, size_t count, int flags,
+                      const uint64_t* h, const uint64_t* z, uint64_t* out_xy, int* out_is_inf, uint64_t* out_Gz) {
+  KZGX_TRY(activate(ctx));
+  if (!shp_shape_ok(n_polys, n_points, n_set_points, n_sets, count, 0, flags) || n == 0 || n > 0xffffffffu ||
+      coeff_stride < n)
+    return KZGX_ERR_ARG;
+  if (!points || !set_point_start || !set_points || !claim_start || !weights || !h || !z || !out_xy || !out_is_inf ||
+      (count > 0 && !poly_index) || (n_polys > 0 && !coeffs))
+    return KZGX_ERR_ARG;
+  const int curve = ctx->c.curve;
+  const size_t nw = (flags & KZGX_SHPLONK_WEIGHT_POWERS) ? 1 : count;
+  if (!multi_canonical(curve, weights, nw) || !multi_canonical(curve, z, 1) || !multi_canonical(curve, h, n))
+    return KZGX_ERR_ARG;
+  KZGX_TRY(shp_structure(curve, poly_index, n_polys, points, n_points, set_point_start, set_points, n_set_points,
+                         claim_start, n_sets, count, SIZE_MAX));
+  if (ctx->c.n_srs == 0) return KZGX_ERR_NO_SRS;
+  if (n - 1 > ctx->c.n_srs) return KZGX_ERR_DEGREE;
+  const size_t pb = point_words(ctx) * 4;
+  const size_t cb = n_polys ? ((n_polys - 1) * coeff_stride + n) * 32 : 32;
+  // inputs: points | weights | z | h | index arrays; outputs: W' | flag | G(z)
+  const ShpIdx il = shp_idx_layout(n_set_points, n_sets, count);
+  const size_t i_w = n_points * 32, i_z = i_w + std::max<size_t>(nw, 1) * 32, i_h = i_z + 32, i_x = i_h + n * 32,
+               i_end = i_x + il.bytes;
+  const size_t o_f = align32(pb), o_g = o_f + 32, o_end = o_g + 32;
+  void *d_c, *d_i, *d_o;
+  KZGX_TRY(stage(ctx, 0, cb, &d_c));
+  KZGX_TRY(stage(ctx, 1, i_end, &d_i));
+  KZGX_TRY(stage(ctx, 2, o_end, &d_o));
+  hipStream_t st = ctx->c.stream;
+  char *in = (char*)d_i, *out = (char*)d_o;
+  if (n_polys) KZGX_TRY_HIP(hipMemcpyAsync(d_c, coeffs, cb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(in, points, n_points * 32, hipMemcpyHostToDevice, st));
+  if (nw) KZGX_TRY_HIP(hipMemcpyAsync(in + i_w, weights, nw * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(in + i_z, z, 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(in + i_h, h, n * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY(shp_idx_copy(in + i_x, il, set_point_start, set_points, n_set_points, claim_start, poly_index, n_sets, count,
+                        st));
+  KZGX_TRY(kzgx_shplonk_open_device(ctx, d_c, n, coeff_stride, n_polys, in, n_points, in + i_x + il.o_sps,
+                                    in + i_x + il.o_sp, n_set_points, in + i_x + il.o_cs, in + i_x + il.o_ix, n_sets,
+                                    in + i_w, count, flags, in + i_h, in + i_z, out, out + o_f, out + o_g, nullptr,
+                                    nullptr));
+  uint32_t inf = 0;
+  KZGX_TRY_HIP(hipMemcpyAsync(out_xy, out, pb, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(&inf, out + o_f, 4, hipMemcpyDeviceToHost, st));
+  if (out_Gz) KZGX_TRY_HIP(hipMemcpyAsync(out_Gz, out + o_g, 32, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  *out_is_inf = (int)inf;
+  return KZGX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the device verify, with the point checks in front when checked
+int shp_verify_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, size_t n_commits,
+                      const void* d_commit_index, const void* d_points, size_t n_points,
+                      const void* d_set_point_start, const void* d_set_points, size_t n_set_points,
+                      const void* d_claim_start, size_t n_sets, const void* d_ys, size_t n_values,
+                      const void* d_weights, size_t count, const void* d_z, const void* d_proof_xy,
+                      const void* d_proof_inf, int flags, bool checked, int subgroup, void* d_ok, void* stream) {
+  KZGX_TRY(activate(ctx));
+  if (!shp_shape_ok(n_commits, n_points, n_set_points, n_sets, count, n_values, flags) || !d_ok) return KZGX_ERR_ARG;
+  if (!d_points || !d_set_point_start || !d_set_points || !d_claim_start || !d_weights || !d_z || !d_proof_xy ||
+      (n_commits > 0 && !d_commits) || (count > 0 && !d_commit_index) || (n_values > 0 && !d_ys))
+    return KZGX_ERR_ARG;
+  if (n_commits + 3 > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  if (ctx->c.n_srs == 0 || ctx->n_srs2 < 2) return KZGX_ERR_NO_SRS;
+  hipStream_t st = pick(ctx, stream);
+  kzgx::Ctx* c = &ctx->c;
+  kzgx::WsLease ws = c->ws_for(st);
+  if (!ws) return KZGX_ERR_ARG;
+  const size_t pw = point_words(ctx);
+  const bool powers = (flags & KZGX_SHPLONK_WEIGHT_POWERS) != 0;
+  uint32_t* f = nullptr;  // commit flags | W, W' flags | their AND
+  if (checked) {
+    KZGX_TRY(chk_scratch(ctx, ws, n_commits + 2 + 1, &f));
+    if (n_commits)
+      KZGX_TRY(kzgx::g1_check2(c, (const uint32_t*)d_commits, (const uint32_t*)d_commit_inf, n_commits,
+                               (const uint32_t*)d_proof_xy, (const uint32_t*)d_proof_inf, 2, subgroup, f, st));
+    else
+      KZGX_TRY(kzgx::g1_check(c, (const uint32_t*)d_proof_xy, (const uint32_t*)d_proof_inf, 2, subgroup, f, st));
+    KZGX_TRY(kzgx::flags_and(f, n_commits + 2, f + n_commits + 2, st));
+  }
+  const size_t ms_words = kzgx::multi_scalars_words(n_commits, n_sets, count);
+  ShpArena a;
+  KZGX_TRY(shp_scratch(ctx, ws,
+                       (2 * n_set_points + n_sets + 1 + (powers ? count : 0) + count + n_commits + 4) * 32 +
+                           align32(ms_words * 4) + align32((n_sets + 1) * 8) + 32 + 10 * 32,
+                       &a));
+  uint32_t* pc = a.take<uint32_t>(n_set_points * 32);
+  uint32_t* pl = a.take<uint32_t>(n_set_points * 32);
+  uint32_t* zeta = a.take<uint32_t>((n_sets + 1) * 32);
+  uint32_t* wexp = a.take<uint32_t>(powers ? count * 32 : 0);
+  uint32_t* rk = a.take<uint32_t>(count * 32);
+  uint32_t* ms = a.take<uint32_t>(ms_words * 4);
+  uint32_t* sc = a.take<uint32_t>((n_commits + 4) * 32);
+  uint64_t* voff = a.take<uint64_t>((n_sets + 1) * 8);
+  uint32_t* gate = a.take<uint32_t>(32);
+  // A | B | flags [A_inf, B_inf, -, -] | z = y = 0
+  KZGX_TRY(kzgx::dev_alloc(c, (void**)&ws->var_pt, (2 * pw + 4 + 16) * 4, &ws->var_pt_b));
+  uint32_t* A = ws->var_pt;
+  uint32_t* B = A + pw;
+  uint32_t* fl = B + pw;
+  uint32_t* zero = fl + 4;
+  KZGX_TRY_HIP(hipMemsetAsync(zero, 0, 64, st));
+  const kzgx::ShpTable t =
+      shp_table(d_points, n_points, d_set_point_start, d_set_points, n_set_points, d_claim_start, n_sets, count);
+  const uint32_t* cidx = (const uint32_t*)d_commit_index;
+  const uint32_t* zp = (const uint32_t*)d_z;
+  KZGX_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)gate, 1, 1, st));
+  KZGX_TRY(kzgx::shp_check(t, cidx, n_commits, gate, st));
+  KZGX_TRY(kzgx::shp_pairs(c, t, zp, pc, pl, gate, st));
+  KZGX_TRY(kzgx::shp_zeta(c, t, zp, zeta, st));
+  KZGX_TRY(kzgx::shp_offsets(t, voff, n_values, gate, st));
+  const uint32_t* wts = (const uint32_t*)d_weights;
+  if (powers) {
+    KZGX_TRY(kzgx::shp_weight_powers(c, wts, count, wexp, st));
+    wts = wexp;
+  }
+  KZGX_TRY(kzgx::shp_interp(c, t, voff, (const uint32_t*)d_ys, n_values, pl, rk, st));
+  // the batch openings' scalars with r_g := zeta_s and y_k := r_k(z): s_c and -t
+  KZGX_TRY(kzgx::multi_scalars(c, cidx, t.claim_start, n_sets, zeta, rk, wts, false, zeta, count, n_commits, ms, st));
+  KZGX_TRY(kzgx::shp_pack(c, ms, n_commits, n_sets, zeta, zp, sc, st));
+  // A = W'
+  const uint32_t* pinf = (const uint32_t*)d_proof_inf;
+  const kzgx::PointSeg sa{(const uint32_t*)d_proof_xy + pw, pinf ? pinf + 1 : nullptr, 1};
+  KZGX_TRY(kzgx::msm_points(c, *ws, &sa, 1, sc + (n_commits + 3) * 8, A, fl, st));
+  // B = sum s_c C_c - t G1[0] - Z_T(z) W + z W'
+  const kzgx::PointSeg sb[3] = {{(const uint32_t*)d_commits, (const uint32_t*)d_commit_inf, n_commits},
+                                {ctx->d_srs_canon, nullptr, 1},
+                                {(const uint32_t*)d_proof_xy, pinf, 2}};
+  const int skip = n_commits ? 0 : 1;  // no empty segment
+  KZGX_TRY(kzgx::msm_points(c, *ws, sb + skip, 3 - skip, sc, B, fl + 1, st));
+  // e(A, [tau]G2) == e(B, G2[0]), as kzgx_verify_aggregate_device's tail
+  KZGX_TRY(kzgx_verify_single_batch_device(ctx, B, fl + 1, A, fl, zero, zero + 8, 1, d_ok, stream));
+  KZGX_TRY(kzgx::flag_gate((uint32_t*)d_ok, gate, st));
+  if (checked) KZGX_TRY(kzgx::flag_gate((uint32_t*)d_ok, f + n_commits + 2, st));
+  return KZGX_OK;
+}
+
+int shp_verify_host(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                    const uint32_t* commit_index, const uint64_t* points, size_t n_points,
+                    const uint32_t* set_point_start, const uint32_t* set_points, size_t n_set_points,
+                    const uint32_t* claim_start, size_t n_sets, const uint64_t* ys, size_t n_values,
+                    const uint64_t* weights, size_t count, const uint64_t* z, const uint64_t* proof_xy,
+                    const int* proof_inf, int flags, bool checked, int subgroup, int* ok) {
+  KZGX_TRY(activate(ctx));
+  if (!shp_shape_ok(n_commits, n_points, n_set_points, n_sets, count, n_values, flags) || !ok) return KZGX_ERR_ARG;
+  if (!points || !set_point_start || !set_points || !claim_start || !weights || !z || !proof_xy ||
+      (n_commits > 0 && !commits_xy) || (count > 0 && !commit_index) || (n_values > 0 && !ys))
+    return KZGX_ERR_ARG;
+  if (n_commits + 3 > KZGX_MSM_POINTS_MAX) return KZGX_ERR_ARG;
+  const int curve = ctx->c.curve;
+  const size_t nw = (flags & KZGX_SHPLONK_WEIGHT_POWERS) ? 1 : count;
+  if (!multi_canonical(curve, weights, nw) || !multi_canonical(curve, z, 1) || !multi_canonical(curve, ys, n_values))
+    return KZGX_ERR_ARG;
+  KZGX_TRY(shp_structure(curve, commit_index, n_commits, points, n_points, set_point_start, set_points, n_set_points,
+                         claim_start, n_sets, count, n_values));
+  if (ctx->c.n_srs == 0 || ctx->n_srs2 < 2) return KZGX_ERR_NO_SRS;
+  const size_t pb = point_words(ctx) * 4;
+  // scalars: points | y | weights | z; words: commit_inf | proof_inf (2) | index arrays | ok
+  const ShpIdx il = shp_idx_layout(n_set_points, n_sets, count);
+  const size_t s_y = n_points * 32, s_w = s_y + n_values * 32, s_z = s_w + std::max<size_t>(nw, 1) * 32, s_end = s_z + 32;
+  const size_t w_p = align32(n_commits * 4), w_x = w_p + 32, w_ok = w_x + il.bytes, w_end = w_ok + 32;
+  void *d_c, *d_p, *d_s, *d_w;
+  KZGX_TRY(stage(ctx, 0, std::max<size_t>(n_commits, 1) * pb, &d_c));
+  KZGX_TRY(stage(ctx, 1, 2 * pb, &d_p));
+  KZGX_TRY(stage(ctx, 2, s_end, &d_s));
+  KZGX_TRY(stage(ctx, 3, w_end, &d_w));
+  std::vector<uint32_t> cf(n_commits + 2, 0u);
+  for (size_t i = 0; i < n_commits; i++) cf[i] = commit_inf ? (uint32_t)(commit_inf[i] != 0) : 0u;
+  for (size_t i = 0; i < 2; i++) cf[n_commits + i] = proof_inf ? (uint32_t)(proof_inf[i] != 0) : 0u;
+  hipStream_t st = ctx->c.stream;
+  char *sc = (char*)d_s, *dw = (char*)d_w;
+  if (n_commits) {
+    KZGX_TRY_HIP(hipMemcpyAsync(d_c, commits_xy, n_commits * pb, hipMemcpyHostToDevice, st));
+    KZGX_TRY_HIP(hipMemcpyAsync(dw, cf.data(), n_commits * 4, hipMemcpyHostToDevice, st));
+  }
+  KZGX_TRY_HIP(hipMemcpyAsync(dw + w_p, cf.data() + n_commits, 8, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(d_p, proof_xy, 2 * pb, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(sc, points, n_points * 32, hipMemcpyHostToDevice, st));
+  if (n_values) KZGX_TRY_HIP(hipMemcpyAsync(sc + s_y, ys, n_values * 32, hipMemcpyHostToDevice, st));
+  if (nw) KZGX_TRY_HIP(hipMemcpyAsync(sc + s_w, weights, nw * 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY_HIP(hipMemcpyAsync(sc + s_z, z, 32, hipMemcpyHostToDevice, st));
+  KZGX_TRY(shp_idx_copy(dw + w_x, il, set_point_start, set_points, n_set_points, claim_start, commit_index, n_sets,
+                        count, st));
+  // the flags are copied before the call below only reads them: the vector outlives the synchronisation
+  KZGX_TRY(shp_verify_device(ctx, d_c, dw, n_commits, dw + w_x + il.o_ix, sc, n_points, dw + w_x + il.o_sps,
+                             dw + w_x + il.o_sp, n_set_points, dw + w_x + il.o_cs, n_sets, sc + s_y, n_values,
+                             sc + s_w, count, sc + s_z, d_p, dw + w_p, flags, checked, subgroup, dw + w_ok, nullptr));
+  uint32_t v = 0;
+  KZGX_TRY_HIP(hipMemcpyAsync(&v, dw + w_ok, 4, hipMemcpyDeviceToHost, st));
+  KZGX_TRY_HIP(hipStreamSynchronize(st));
+  *ok = v ? 1 : 0;
+  return KZGX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kzgx_shplonk_verify_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf, size_t n_commits,
+                               const void* d_commit_index, const void* d_points, size_t n_points,
+                               const void* d_set_point_start, const void* d_set_points, size_t n_set_points,
+                               const void* d_claim_start, size_t n_sets, const void* d_ys, size_t n_values,
+                               const void* d_weights, size_t count, const void* d_z, const void* d_proof_xy,
+                               const void* d_proof_inf, int flags, void* d_ok, void* stream) {
+  return shp_verify_device(ctx, d_commits, d_commit_inf, n_commits, d_commit_index, d_points, n_points,
+                           d_set_point_start, d_set_points, n_set_points, d_claim_start, n_sets, d_ys, n_values,
+                           d_weights, count, d_z, d_proof_xy, d_proof_inf, flags, false, 0, d_ok, stream);
+}
+
+int kzgx_shplonk_verify_checked_device(kzgx_ctx* ctx, const void* d_commits, const void* d_commit_inf,
+                                       size_t n_commits, const void* d_commit_index, const void* d_points,
+                                       size_t n_points, const void* d_set_point_start, const void* d_set_points,
+                                       size_t n_set_points, const void* d_claim_start, size_t n_sets,
+                                       const void* d_ys, size_t n_values, const void* d_weights, size_t count,
+                                       const void* d_z, const void* d_proof_xy, const void* d_proof_inf, int flags,
+                                       int subgroup, void* d_ok, void* stream) {
+  return shp_verify_device(ctx, d_commits, d_commit_inf, n_commits, d_commit_index, d_points, n_points,
+                           d_set_point_start, d_set_points, n_set_points, d_claim_start, n_sets, d_ys, n_values,
+                           d_weights, count, d_z, d_proof_xy, d_proof_inf, flags, true, subgroup, d_ok, stream);
+}
+
+int kzgx_shplonk_verify(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                        const uint32_t* commit_index, const uint64_t* points, size_t n_points,
+                        const uint32_t* set_point_start, const uint32_t* set_points, size_t n_set_points,
+                        const uint32_t* claim_start, size_t n_sets, const uint64_t* ys, size_t n_values,
+                        const uint64_t* weights, size_t count, const uint64_t* z, const uint64_t* proof_xy,
+                        const int* proof_inf, int flags, int* ok) {
+  return shp_verify_host(ctx, commits_xy, commit_inf, n_commits, commit_index, points, n_points, set_point_start,
+                         set_points, n_set_points, claim_start, n_sets, ys, n_values, weights, count, z, proof_xy,
+                         proof_inf, flags, false, 0, ok);
+}
+
+int kzgx_shplonk_verify_checked(kzgx_ctx* ctx, const uint64_t* commits_xy, const int* commit_inf, size_t n_commits,
+                                const uint32_t* commit_index, const uint64_t* points, size_t n_points,
+                                const uint32_t* set_point_start, const uint32_t* set_points, size_t n_set_points,
+                                const uint32_t* claim_start, size_t n_sets, const uint64_t* ys, size_t n_values,
+                                const uint64_t* weights, size_t count, const uint64_t* z, const uint64_t* proof_xy,
+                                const int* proof_inf, int flags, int subgroup, int* ok) {
+  return shp_verify_host(ctx, commits_xy, commit_inf, n_commits, commit_index, points, n_points, set_point_start,
+                         set_points, n_set_points, claim_start, n_sets, ys, n_values, weights, count, z, proof_xy,
+                         proof_inf, flags, true, subgroup, ok);
 }
 
 }  // extern "C"

@@ -59,6 +59,9 @@ EXPORTS = [
     "kzgx_prove_multi_batch", "kzgx_prove_multi_batch_device", "kzgx_verify_multi_batch",
     "kzgx_verify_multi_batch_device", "kzgx_verify_multi_batch_checked", "kzgx_verify_multi_batch_checked_device",
     "kzgx_set_multi_chunk",
+    "kzgx_shplonk_commit", "kzgx_shplonk_commit_device", "kzgx_shplonk_open", "kzgx_shplonk_open_device",
+    "kzgx_shplonk_verify", "kzgx_shplonk_verify_device", "kzgx_shplonk_verify_checked",
+    "kzgx_shplonk_verify_checked_device", "kzgx_set_shplonk_chunk",
 ]
 
 
@@ -97,6 +100,13 @@ SRS_STRUCT_GENERATORS = _header_define("KZGX_SRS_STRUCT_GENERATORS")
 MULTI_WEIGHT_POWERS = _header_define("KZGX_MULTI_WEIGHT_POWERS")
 MULTI_CHUNK_SCALARS = _header_define("KZGX_MULTI_CHUNK_SCALARS")
 MULTI_EVAL_SLICE = _header_define("KZGX_MULTI_EVAL_SLICE")
+# Shplonk openings: weights are one gamma (w_k = gamma^k), the most points per set and in T, the scalars per
+# internal chunk of folded polynomials, and the coefficients per workgroup of the fused quotient
+SHPLONK_WEIGHT_POWERS = _header_define("KZGX_SHPLONK_WEIGHT_POWERS")
+SHPLONK_SET_MAX = _header_define("KZGX_SHPLONK_SET_MAX")
+SHPLONK_POINTS_MAX = _header_define("KZGX_SHPLONK_POINTS_MAX")
+SHPLONK_CHUNK_SCALARS = _header_define("KZGX_SHPLONK_CHUNK_SCALARS")
+SHPLONK_TILE = _header_define("KZGX_SHPLONK_TILE")
 
 _lib = None
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -311,6 +321,25 @@ def lib():
             "kzgx_verify_multi_batch_checked_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp,
                                                                       vp, sz, ctypes.c_int, ctypes.c_int, vp, vp]),
             "kzgx_set_multi_chunk": (ctypes.c_int, [vp, sz]),
+            "kzgx_shplonk_commit": (ctypes.c_int, [vp, u64p, sz, sz, sz, u64p, sz, u32p, u32p, sz, u32p, u32p, sz,
+                                                   u64p, sz, sz, ctypes.c_int, u64p, intp, u64p, u64p]),
+            "kzgx_shplonk_commit_device": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz,
+                                                          sz, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+            "kzgx_shplonk_open": (ctypes.c_int, [vp, u64p, sz, sz, sz, u64p, sz, u32p, u32p, sz, u32p, u32p, sz, u64p,
+                                                 sz, ctypes.c_int, u64p, u64p, u64p, intp, u64p]),
+            "kzgx_shplonk_open_device": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz,
+                                                        ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]),
+            "kzgx_shplonk_verify": (ctypes.c_int, [vp, u64p, intp, sz, u32p, u64p, sz, u32p, u32p, sz, u32p, sz, u64p,
+                                                   sz, u64p, sz, u64p, u64p, intp, ctypes.c_int, intp]),
+            "kzgx_shplonk_verify_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz, vp, sz, vp,
+                                                          sz, vp, vp, vp, ctypes.c_int, vp, vp]),
+            "kzgx_shplonk_verify_checked": (ctypes.c_int, [vp, u64p, intp, sz, u32p, u64p, sz, u32p, u32p, sz, u32p,
+                                                           sz, u64p, sz, u64p, sz, u64p, u64p, intp, ctypes.c_int,
+                                                           ctypes.c_int, intp]),
+            "kzgx_shplonk_verify_checked_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz, vp,
+                                                                  sz, vp, sz, vp, vp, vp, ctypes.c_int, ctypes.c_int,
+                                                                  vp, vp]),
+            "kzgx_set_shplonk_chunk": (ctypes.c_int, [vp, sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -1068,6 +1097,139 @@ class Context:
     def set_multi_chunk(self, scalars: int) -> None:
         """test knob: scalars of folded polynomials per internal chunk of prove_multi (0 = the default)"""
         _chk(lib().kzgx_set_multi_chunk(self.h, scalars), "kzgx_set_multi_chunk")
+
+    # ---- Shplonk openings: many polynomials at different point sets, one two-point proof ----
+    @staticmethod
+    def _shplonk_table(points, sets):
+        """sets: a list of (point indices, claim indices) pairs -> points, set_point_start, set_points,
+        claim_start, claim index array (uint32)"""
+        t = as_scalars(points)
+        sps, sp, cs, ix = [0], [], [0], []
+        for pts, claims in sets:
+            sp += [int(v) for v in pts]
+            ix += [int(v) for v in claims]
+            sps.append(len(sp))
+            cs.append(len(ix))
+        u32 = lambda v: np.ascontiguousarray(np.array(v, dtype=np.uint32).reshape(-1))  # noqa: E731
+        return t, u32(sps), u32(sp), u32(cs), u32(ix)
+
+    def shplonk_commit(self, polys, points, sets, weights, powers: bool = False, n: int | None = None,
+                       want_y: bool = True):
+        """kzgx_shplonk_commit.  polys: (n_polys, stride, 4), the first n coefficients of a row used; points: T;
+        sets: a list of (indices into T, polynomial indices of the set's claims); weights: one scalar per claim,
+        or one gamma with powers (w_k = gamma^k).  Returns W, its infinity flag, h ((n, 4)) and the values
+        ((n_values, 4), claim by claim in the set's point order; None without want_y)."""
+        c = np.ascontiguousarray(polys, dtype=np.uint64)
+        assert c.ndim == 3 and c.shape[2] == 4
+        n_polys, stride = c.shape[0], c.shape[1]
+        n = stride if n is None else n
+        t, sps, sp, cs, pi = self._shplonk_table(points, sets)
+        w = np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1, 4)
+        count = pi.shape[0]
+        assert w.shape[0] == (1 if powers else count)
+        n_values = sum(len(p) * len(k) for p, k in sets)
+        out = np.zeros(2 * self.w64, dtype=np.uint64)
+        inf = ctypes.c_int(0)
+        h = np.zeros((n, 4), dtype=np.uint64)
+        y = np.zeros((n_values, 4), dtype=np.uint64) if want_y else None
+        _chk(lib().kzgx_shplonk_commit(self.h, _p(c), n, stride, n_polys, _p(t), t.shape[0],
+                                       sps.ctypes.data_as(u32p), sp.ctypes.data_as(u32p), sp.shape[0],
+                                       cs.ctypes.data_as(u32p), pi.ctypes.data_as(u32p), len(sets), _p(w), count,
+                                       n_values, SHPLONK_WEIGHT_POWERS if powers else 0, _p(out), ctypes.byref(inf),
+                                       _p(h), _p(y)), "kzgx_shplonk_commit")
+        return out, bool(inf.value), h, y
+
+    def shplonk_commit_device(self, d_coeffs, n, stride, n_polys, d_points, n_points, d_set_point_start, d_set_points,
+                              n_set_points, d_claim_start, d_poly_index, n_sets, d_weights, count, n_values, d_out,
+                              d_inf, d_h, d_y=None, d_ok=None, powers=False, stream=None):
+        """kzgx_shplonk_commit_device: device pointers (indices uint32), d_ok one uint32 or None, enqueued on
+        stream."""
+        _chk(lib().kzgx_shplonk_commit_device(self.h, d_coeffs, n, stride, n_polys, d_points, n_points,
+                                              d_set_point_start, d_set_points, n_set_points, d_claim_start,
+                                              d_poly_index, n_sets, d_weights, count, n_values,
+                                              SHPLONK_WEIGHT_POWERS if powers else 0, d_out, d_inf, d_h, d_y, d_ok,
+                                              stream), "kzgx_shplonk_commit_device")
+
+    def shplonk_open(self, polys, points, sets, weights, h, z, powers: bool = False, n: int | None = None):
+        """kzgx_shplonk_open: the table of shplonk_commit, its h and the challenge z.  Returns W', its infinity
+        flag and G(z)."""
+        c = np.ascontiguousarray(polys, dtype=np.uint64)
+        assert c.ndim == 3 and c.shape[2] == 4
+        n_polys, stride = c.shape[0], c.shape[1]
+        n = stride if n is None else n
+        t, sps, sp, cs, pi = self._shplonk_table(points, sets)
+        w = np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1, 4)
+        count = pi.shape[0]
+        assert w.shape[0] == (1 if powers else count)
+        hh = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, 4)
+        assert hh.shape[0] == n
+        zz = as_scalars(z).reshape(-1, 4)
+        out = np.zeros(2 * self.w64, dtype=np.uint64)
+        inf = ctypes.c_int(0)
+        gz = np.zeros(4, dtype=np.uint64)
+        _chk(lib().kzgx_shplonk_open(self.h, _p(c), n, stride, n_polys, _p(t), t.shape[0], sps.ctypes.data_as(u32p),
+                                     sp.ctypes.data_as(u32p), sp.shape[0], cs.ctypes.data_as(u32p),
+                                     pi.ctypes.data_as(u32p), len(sets), _p(w), count,
+                                     SHPLONK_WEIGHT_POWERS if powers else 0, _p(hh), _p(zz), _p(out),
+                                     ctypes.byref(inf), _p(gz)), "kzgx_shplonk_open")
+        return out, bool(inf.value), gz
+
+    def shplonk_open_device(self, d_coeffs, n, stride, n_polys, d_points, n_points, d_set_point_start, d_set_points,
+                            n_set_points, d_claim_start, d_poly_index, n_sets, d_weights, count, d_h, d_z, d_out,
+                            d_inf, d_Gz=None, d_ok=None, powers=False, stream=None):
+        """kzgx_shplonk_open_device: device pointers, d_ok one uint32 or None, enqueued on stream."""
+        _chk(lib().kzgx_shplonk_open_device(self.h, d_coeffs, n, stride, n_polys, d_points, n_points,
+                                            d_set_point_start, d_set_points, n_set_points, d_claim_start,
+                                            d_poly_index, n_sets, d_weights, count,
+                                            SHPLONK_WEIGHT_POWERS if powers else 0, d_h, d_z, d_out, d_inf, d_Gz, d_ok,
+                                            stream), "kzgx_shplonk_open_device")
+
+    def shplonk_verify(self, commits, points, sets, ys, weights, z, proof, powers: bool = False, commit_inf=None,
+                       proof_inf=None, checked: bool = False, subgroup: int = 0) -> bool:
+        """kzgx_shplonk_verify(_checked): sets as for shplonk_commit with commitment indices for the claims; ys: the
+        n_values values in shplonk_commit's layout; proof: W then W' ((2, 2 * w64)); checked: the G1 check of
+        every commitment, W and W' in front."""
+        c = np.ascontiguousarray(commits, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        p = np.ascontiguousarray(proof, dtype=np.uint64).reshape(-1, 2 * self.w64)
+        assert p.shape[0] == 2
+        t, sps, sp, cs, ci = self._shplonk_table(points, sets)
+        count, n_commits = ci.shape[0], c.shape[0]
+        n_values = sum(len(a) * len(b) for a, b in sets)
+        y = as_scalars(ys) if n_values else np.zeros((0, 4), dtype=np.uint64)
+        w = np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1, 4)
+        assert y.shape[0] == n_values and w.shape[0] == (1 if powers else count)
+        zz = as_scalars(z).reshape(-1, 4)
+        fc = None if commit_inf is None else np.ascontiguousarray(commit_inf, dtype=np.int32)
+        fp = None if proof_inf is None else np.ascontiguousarray(proof_inf, dtype=np.int32)
+        ok = ctypes.c_int(0)
+        args = [self.h, _p(c), None if fc is None else fc.ctypes.data_as(intp), n_commits, ci.ctypes.data_as(u32p),
+                _p(t), t.shape[0], sps.ctypes.data_as(u32p), sp.ctypes.data_as(u32p), sp.shape[0],
+                cs.ctypes.data_as(u32p), len(sets), _p(y), n_values, _p(w), count, _p(zz), _p(p),
+                None if fp is None else fp.ctypes.data_as(intp), SHPLONK_WEIGHT_POWERS if powers else 0]
+        if checked:
+            _chk(lib().kzgx_shplonk_verify_checked(*args, int(bool(subgroup)), ctypes.byref(ok)),
+                 "kzgx_shplonk_verify_checked")
+        else:
+            _chk(lib().kzgx_shplonk_verify(*args, ctypes.byref(ok)), "kzgx_shplonk_verify")
+        return bool(ok.value)
+
+    def shplonk_verify_device(self, d_commits, d_commit_inf, n_commits, d_commit_index, d_points, n_points,
+                              d_set_point_start, d_set_points, n_set_points, d_claim_start, n_sets, d_ys, n_values,
+                              d_weights, count, d_z, d_proof, d_proof_inf, d_ok, powers=False, checked=False,
+                              subgroup=0, stream=None):
+        """kzgx_shplonk_verify(_checked)_device: device pointers, d_ok one uint32, enqueued on stream."""
+        args = [self.h, d_commits, d_commit_inf, n_commits, d_commit_index, d_points, n_points, d_set_point_start,
+                d_set_points, n_set_points, d_claim_start, n_sets, d_ys, n_values, d_weights, count, d_z, d_proof,
+                d_proof_inf, SHPLONK_WEIGHT_POWERS if powers else 0]
+        if checked:
+            _chk(lib().kzgx_shplonk_verify_checked_device(*args, int(bool(subgroup)), d_ok, stream),
+                 "kzgx_shplonk_verify_checked_device")
+        else:
+            _chk(lib().kzgx_shplonk_verify_device(*args, d_ok, stream), "kzgx_shplonk_verify_device")
+
+    def set_shplonk_chunk(self, scalars: int) -> None:
+        """test knob: scalars of folded polynomials per internal chunk of shplonk_commit (0 = the default)"""
+        _chk(lib().kzgx_set_shplonk_chunk(self.h, scalars), "kzgx_set_shplonk_chunk")
 
     # ---- evaluation form: Fr NTT, commits and openings from evaluations ----
     def ntt(self, a, inverse: bool = False, bitrev: bool = False) -> np.ndarray:

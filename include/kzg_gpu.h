@@ -189,6 +189,27 @@ int kzgx_fixed_window_info(const kzgx_ctx* ctx, int* c, size_t* bytes);
  * blocks / ranges entries and the Horner pass folds ranges times the
  * partials; 0 = automatic: 1; <= 8; $KZGX_FIXED_JOINT_RANGES at kzgx_create) */
 int kzgx_set_fixed_joint_ranges(kzgx_ctx* ctx, unsigned ranges);
+/* Residency reserve of the block table's accumulation: wave slots per CU
+ * that its launches leave free, so that the tail passes of a call on another
+ * stream (Horner stages, finish, the quotient) find registers beside it
+ * instead of waiting for a residency boundary.  Held by an unused dynamic
+ * LDS size per workgroup, the smallest for which the device's occupancy
+ * query answers r workgroups fewer; the kernel and its results are the same
+ * at every r.  r = 0: none (the plain launch); r = -1: the curve's default
+ * (the default, or $KZGX_FIXED_ACCUM_RESERVE read at kzgx_create); an r
+ * beyond what 64 KiB of dynamic LDS can hold back is clamped (at least one
+ * workgroup per CU stays); r < -1: KZGX_ERR_ARG.  Takes effect with the next
+ * call. */
+int kzgx_set_fixed_accum_reserve(kzgx_ctx* ctx, int r);
+/* the request (-1 = default), the reserve in effect for the accumulation
+ * kernel the next call launches, the dynamic LDS bytes per workgroup that
+ * hold it (0 with no reserve), and which kernel that is: bit 0 = the one that
+ * tests for table entries at infinity (the built table has some), bit 1 =
+ * the endomorphism split's.  Only the split's tail is fitted to the room a
+ * reserve leaves (stage 2 in half-wavefront workgroups, the tail kernels'
+ * issue priority); with KZGX_FIXED_JOINT_GLV=0 a reserve holds the slots
+ * back but stage 2 keeps its full LDS and still waits for a residency. */
+int kzgx_fixed_accum_reserve_info(const kzgx_ctx* ctx, int* request, int* reserve, size_t* lds_bytes, int* variant);
 /* device bytes a table of window c over n_points would take (no context) */
 int kzgx_fixed_base_bytes(int curve, int c, size_t n_points, size_t* bytes);
 /* bounded-memory precompute: the widest supported window c <= 17 whose

@@ -50,6 +50,7 @@ __global__ __launch_bounds__(64) void k_joint_horner1(const uint32_t* __restrict
                                                       uint32_t* __restrict__ segs) {
   constexpr int XW = xyzz_words<C>();
   constexpr uint32_t BITS = GLV ? JOINT_PL : C::SCALAR_BITS;
+  __builtin_amdgcn_s_setprio(3);  // a tail pass: issue ahead of a co-resident accumulation (msm_joint.hip "Tail priority")
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= lanes) return;  // lanes = batch R JOINT_NSEG
   const uint64_t br = t / JOINT_NSEG;
@@ -111,17 +112,22 @@ __global__ __launch_bounds__(64) void k_joint_horner2(const uint32_t* __restrict
 
 // stage 2 of the endomorphism split: two adjacent 8-lane groups per MSM, group
 // (b, h) folds half h's JOINT_NSEG / 2 segment sums of every range: 127
-// cooperative doublings, not 253.  sums[b][h].
-template <class C>
+// cooperative doublings, not 253.  sums[b][h].  GPW groups per workgroup
+// (block size GPW COOP_G): 8 fill the wavefront; 4 halve the workgroup's LDS
+// (BN254 5760 B, not 11 520 B), which is what a CU has left beside an
+// accumulation that runs with a residency reserve (msm_joint.hip).
+template <class C, int GPW>
 __global__ __launch_bounds__(64) void k_joint_horner2_glv(const uint32_t* __restrict__ segs, uint32_t batch, uint32_t R,
                                                           uint32_t* __restrict__ sums) {
   constexpr int XW = xyzz_words<C>();
   constexpr int L = C::Fp29::L;
   constexpr uint32_t HSEG = JOINT_NSEG / 2;
-  __shared__ uint32_t sc[(64 / COOP_G) * COOP_SLOTS * L];
+  static_assert(GPW * COOP_G <= 64, "one wavefront");
+  __shared__ uint32_t sc[GPW * COOP_SLOTS * L];
+  __builtin_amdgcn_s_setprio(3);  // a tail pass: issue ahead of a co-resident accumulation (msm_joint.hip "Tail priority")
   const uint32_t grp = threadIdx.x / COOP_G;
   const int j = (int)(threadIdx.x % COOP_G);
-  const uint32_t gid = blockIdx.x * (64 / COOP_G) + grp;
+  const uint32_t gid = blockIdx.x * GPW + grp;
   const uint32_t b = gid >> 1, h = gid & 1u;
   if (b >= batch) return;
   uint32_t* my = sc + grp * COOP_SLOTS * L;
@@ -153,12 +159,17 @@ __global__ __launch_bounds__(64) void k_joint_finish_glv(const uint32_t* __restr
                                                          uint32_t* __restrict__ out, uint32_t* __restrict__ out_inf) {
   using F = typename C::Fp29;
   constexpr int XW = xyzz_words<C>();
+  __builtin_amdgcn_s_setprio(3);  // a tail pass: issue ahead of a co-resident accumulation (msm_joint.hip "Tail priority")
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= batch) return;
   const Xyzz<C> s1 = xyzz_load<C>(sums + (size_t)(2 * b) * XW);
   Xyzz<C> s2 = xyzz_load<C>(sums + (size_t)(2 * b + 1) * XW);
   s2.X = f29_mul<F>(s2.X, f29_const<F>(C::Glv::BETA29));  // < 2m
-  const Xyzz<C> p = xyzz_add<C>(s1, s2);
+  // inlined: the call's frame made this kernel 226 / 248 VGPRs with 568 / 892 B
+  // of scratch; inlined 162 / 248 with 280 / 444 B, so that on BN254 it fits
+  // beside two of the accumulation's wavefronts per SIMD (msm_joint.hip
+  // "Residency reserve")
+  const Xyzz<C> p = xyzz_add_impl<C>(s1, s2);
   Affine<C> a;
   const bool fin = xyzz_to_affine<C>(p, a);
   affine_to_canonical<C>(out + (size_t)b * 2 * C::Fp::N, a, fin);
@@ -167,21 +178,26 @@ __global__ __launch_bounds__(64) void k_joint_finish_glv(const uint32_t* __restr
 
 template <class C>
 int joint_horner_glv_launch(const uint32_t* part, uint32_t batch, uint32_t R, uint32_t* segs, uint32_t* sums,
-                            uint32_t* out, uint32_t* out_inf, hipStream_t st) {
+                            uint32_t* out, uint32_t* out_inf, bool narrow, hipStream_t st) {
   static_assert(JOINT_PL == 256 && (JOINT_NSEG & 1u) == 0, "two halves of 128 planes, whole segments each");
   const uint64_t lanes = (uint64_t)batch * R * JOINT_NSEG;
   if (batch == 0 || batch > 0x3fffffffu || R == 0 || (lanes + 63) / 64 > 0x7fffffffull) return KZGX_ERR_ARG;
   hipLaunchKernelGGL((k_joint_horner1<C, true>), dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, part, lanes,
                      segs);
-  constexpr uint32_t GPW = 64 / COOP_G;  // groups per workgroup
-  hipLaunchKernelGGL(k_joint_horner2_glv<C>, dim3((2 * batch + GPW - 1) / GPW), dim3(64), 0, st, segs, batch, R, sums);
+  constexpr uint32_t GPW = 64 / COOP_G;  // groups per workgroup; half of them beside a reserved residency
+  if (narrow)
+    hipLaunchKernelGGL((k_joint_horner2_glv<C, GPW / 2>), dim3((2 * batch + GPW / 2 - 1) / (GPW / 2)),
+                       dim3(COOP_G * GPW / 2), 0, st, segs, batch, R, sums);
+  else
+    hipLaunchKernelGGL((k_joint_horner2_glv<C, GPW>), dim3((2 * batch + GPW - 1) / GPW), dim3(64), 0, st, segs, batch,
+                       R, sums);
   hipLaunchKernelGGL(k_joint_finish_glv<C>, dim3((batch + 63) / 64), dim3(64), 0, st, sums, batch, out, out_inf);
   return KZGX_OK;
 }
 template int joint_horner_glv_launch<BN254G1>(const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t*,
-                                              uint32_t*, hipStream_t);
+                                              uint32_t*, bool, hipStream_t);
 template int joint_horner_glv_launch<BLS12381G1>(const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t*,
-                                                 uint32_t*, hipStream_t);
+                                                 uint32_t*, bool, hipStream_t);
 
 template <class C>
 int joint_horner_launch(const uint32_t* part, uint32_t batch, uint32_t R, uint32_t* segs, uint32_t* sums,

@@ -598,11 +598,23 @@ int kzgx_create(kzgx_ctx** out, int curve, int device) {
     const int r = atoi(e);
     if (r >= 0 && r <= 8) ctx->c.fixed.joint.ranges = (uint32_t)r;
   }
+  // the block table accumulation's residency reserve: the curve's default
+  // unless set (-1, or wave slots per CU left free; anything else is ignored)
+  if (const char* e = getenv("KZGX_FIXED_ACCUM_RESERVE")) {
+    char* end = nullptr;
+    const long r = strtol(e, &end, 10);
+    if (end != e && !*end && r >= -1 && r <= 64) ctx->c.fixed.joint.reserve_req = (int)r;
+  }
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = stream_take(device, &ctx->c.stream);
   if (e != hipSuccess) {
     delete ctx;
     return kzgx::hip_fail(e);
+  }
+  if (const int rc = kzgx::joint_reserve_resolve(curve, ctx->c.fixed.joint)) {
+    stream_give(device, ctx->c.stream);
+    delete ctx;
+    return rc;
   }
   kzgx::ctx_live_add(device, +1);
   *out = ctx;
@@ -826,6 +838,28 @@ int kzgx_set_fixed_joint_ranges(kzgx_ctx* ctx, unsigned ranges) {
   KZGX_TRY(activate(ctx));
   if (ranges > 8) return KZGX_ERR_ARG;  // 0 = automatic
   ctx->c.fixed.joint.ranges = ranges;
+  return KZGX_OK;
+}
+
+int kzgx_set_fixed_accum_reserve(kzgx_ctx* ctx, int r) {
+  KZGX_TRY(activate(ctx));
+  if (r < -1) return KZGX_ERR_ARG;  // -1 = the curve's default; an over-large r is clamped
+  kzgx::JointTable& jt = ctx->c.fixed.joint;
+  const int keep = jt.reserve_req;
+  jt.reserve_req = r;
+  const int rc = kzgx::joint_reserve_resolve(ctx->c.curve, jt);  // later launches only
+  if (rc != KZGX_OK) jt.reserve_req = keep;
+  return rc;
+}
+
+int kzgx_fixed_accum_reserve_info(const kzgx_ctx* ctx, int* request, int* reserve, size_t* lds_bytes, int* variant) {
+  if (!ctx) return KZGX_ERR_ARG;
+  const kzgx::JointTable& jt = ctx->c.fixed.joint;
+  const int v = (jt.glv ? 2 : 0) + (jt.n_inf ? 1 : 0);  // the kernel variant the next call launches
+  if (request) *request = jt.reserve_req;
+  if (reserve) *reserve = jt.reserve[v];
+  if (lds_bytes) *lds_bytes = jt.reserve_lds[v];
+  if (variant) *variant = v;
   return KZGX_OK;
 }
 

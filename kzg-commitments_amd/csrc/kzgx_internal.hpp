@@ -133,6 +133,14 @@ struct JointTable {
   int g_req = 0;        // -1 automatic, 0 off, 2..25 forced (kzgx_set_fixed_joint)
   uint32_t ranges = 0;  // block ranges per MSM of the accumulation, 0 = automatic
   bool glv = false;     // split every scalar with the curve endomorphism: 2 x 128 planes (KZGX_FIXED_JOINT_GLV)
+  // the accumulation's residency reserve (msm_joint.hip "Residency reserve"):
+  // wave slots per CU its launch leaves free, -1 = the curve's default
+  // (kzgx_set_fixed_accum_reserve, KZGX_FIXED_ACCUM_RESERVE); what
+  // joint_reserve_resolve made of it per kernel variant [2 glv + inf]: the
+  // reserve in effect and the unused dynamic LDS bytes per workgroup that hold it
+  int reserve_req = -1;
+  int reserve[4] = {0, 0, 0, 0};
+  uint32_t reserve_lds[4] = {0, 0, 0, 0};
   int g = 0;            // built table
   uint32_t blocks = 0;
   size_t n_t = 0;
@@ -389,13 +397,19 @@ int joint_horner_launch(const uint32_t* part, uint32_t batch, uint32_t R, uint32
                         hipStream_t st);
 // the endomorphism split's pass: planes [0, 128) and [128, 256) are the two
 // halves' own sums S_1, S_2 (all JOINT_PL planes live); sums: 2 batch records;
-// out = S_1 + phi(S_2), canonical affine and infinity flags as k_fixed_finish's
+// out = S_1 + phi(S_2), canonical affine and infinity flags as k_fixed_finish's;
+// narrow: stage 2 in half-wavefront workgroups with half the LDS (beside a
+// reserved residency of the accumulation)
 template <class C>
 int joint_horner_glv_launch(const uint32_t* part, uint32_t batch, uint32_t R, uint32_t* segs, uint32_t* sums,
-                            uint32_t* out, uint32_t* out_inf, hipStream_t st);
+                            uint32_t* out, uint32_t* out_inf, bool narrow, hipStream_t st);
 // the split's default for a curve, and the split of count host scalars as the
 // index pass forms it (9 words each: |k1|, |k2|, sign bits) to host out
 bool joint_glv_default(int curve);
+// the accumulation's residency reserve: the default for a curve, and jt.reserve_req
+// resolved against the current device's occupancy query into jt.reserve / jt.reserve_lds
+int joint_reserve_default(int curve);
+int joint_reserve_resolve(int curve, JointTable& jt);
 int joint_glv_debug(Ctx* ctx, const uint32_t* scalars, size_t count, uint32_t* out);
 int srs_upload(Ctx* ctx, const uint32_t* d_canon, size_t n);
 // mixed additions / s of the fixed-base accumulation loop on L1-resident operands (msm_fixed.hip)

@@ -444,6 +444,7 @@ __global__ __launch_bounds__(64) void k_joint_index(const uint32_t* __restrict__
                                                     size_t stride_words, uint32_t n_t, uint32_t g, uint32_t nb,
                                                     uint32_t* __restrict__ idx) {
   constexpr int BITS = C::SCALAR_BITS;
+  __builtin_amdgcn_s_setprio(3);  // a tail pass: issue ahead of a co-resident accumulation (msm_joint.hip "Tail priority")
   const uint32_t b = blockIdx.y, lane = threadIdx.x;
   const uint32_t hi = lane >> 5, li = lane & 31u;
   const uint32_t blk = 2 * blockIdx.x + hi;
@@ -560,6 +561,87 @@ __global__ __launch_bounds__(64, fixed_accum_waves<C>()) void k_joint_accum(
 // table").
 bool joint_glv_default(int curve) { return curve == KZGX_CURVE_BN254 || curve == KZGX_CURVE_BLS12381; }
 
+// Residency reserve.  The accumulation's one-wave workgroups fill every wave
+// slot their registers allow and free them only at residency boundaries, so
+// the other stream's tail passes (stage 1, stage 2, finish, the quotient)
+// wait a whole residency each for registers.  A launch with r > 0 asks for
+// an unused dynamic LDS size under which a CU admits r workgroups fewer: the
+// kernel's code is the same, r wave slots per CU with their registers stay
+// free, and the tails run beside the accumulation (DESIGN.md "Block table").
+// The size is the smallest for which the occupancy query answers full - r,
+// found by bisection (the answer does not rise with the size); r is clamped
+// to what a launch's 64 KiB of dynamic LDS can hold back, which leaves at
+// least one workgroup per CU.  (The query divides the CU's 160 KiB by the
+// byte size; the hardware hands LDS out in granules of 1280 B.  For the
+// smallest size of a given answer both agree: profiles/accum_reserve_probe.txt.)
+//
+// Measured (DESIGN.md "Tail priority and the residency reserve"): the
+// accumulation is issue-bound, so the reserve costs no throughput, but a
+// launch on its own gets longer and the two-stream line did not win that
+// back.  The default is 0 on both curves; the setter stays for A/B runs.
+// Only the endomorphism split's tail is fitted to the room a reserve leaves.
+//
+// Tail priority.  What does make room for the tails is issue priority: the
+// index pass, the Horner stages, the finish and the quotient raise their
+// wavefronts' priority (s_setprio 3) as they start.  They are short dependent
+// chains that need few issue slots, so the accumulation beside them loses
+// little, and a tail that no longer crawls behind three accumulation
+// wavefronts per SIMD hands its stream's next accumulation to the queue
+// while the other stream's is still resident (figures: DESIGN.md).
+constexpr size_t JOINT_RESERVE_LDS_MAX = 65536;
+
+int joint_reserve_default(int curve) {
+  (void)curve;  // 0 on both curves: see above
+  return 0;
+}
+
+template <class C>
+static int joint_reserve_resolve_impl(JointTable& jt, int req) {
+  int rs[4] = {0, 0, 0, 0};  // committed to jt only when every query went through
+  uint32_t ls[4] = {0, 0, 0, 0};
+  for (int v = 0; v < 4; v++) {
+    if (req == 0) continue;
+    auto occ = [&](size_t lds, int* out) {
+      switch (v) {
+        case 0: return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k_joint_accum<C, false, false>, 64, lds);
+        case 1: return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k_joint_accum<C, true, false>, 64, lds);
+        case 2: return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k_joint_accum<C, false, true>, 64, lds);
+        default: return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k_joint_accum<C, true, true>, 64, lds);
+      }
+    };
+    int full = 0, least = 0;
+    KZGX_TRY_HIP(occ(0, &full));
+    KZGX_TRY_HIP(occ(JOINT_RESERVE_LDS_MAX, &least));
+    if (full < 1) return KZGX_ERR_HIP;
+    const int target = std::max(full - std::min(req, full), std::max(least, 1));
+    if (target >= full) continue;
+    size_t lo = 0, hi = JOINT_RESERVE_LDS_MAX;  // occ(lo) > target >= occ(hi)
+    while (hi - lo > 1) {
+      const size_t mid = lo + (hi - lo) / 2;
+      int o = 0;
+      KZGX_TRY_HIP(occ(mid, &o));
+      if (o > target) lo = mid;
+      else hi = mid;
+    }
+    int got = 0;
+    KZGX_TRY_HIP(occ(hi, &got));
+    if (got < 1 || got >= full) return KZGX_ERR_HIP;
+    rs[v] = full - got;
+    ls[v] = (uint32_t)hi;
+  }
+  for (int v = 0; v < 4; v++) {
+    jt.reserve[v] = rs[v];
+    jt.reserve_lds[v] = ls[v];
+  }
+  return KZGX_OK;
+}
+
+int joint_reserve_resolve(int curve, JointTable& jt) {
+  const int req = jt.reserve_req < 0 ? joint_reserve_default(curve) : jt.reserve_req;
+  return curve == KZGX_CURVE_BN254 ? joint_reserve_resolve_impl<BN254G1>(jt, req)
+                                   : joint_reserve_resolve_impl<BLS12381G1>(jt, req);
+}
+
 bool joint_serves(const FixedTable& ft, size_t n, size_t batch, bool xyzz_out) {
   const JointTable& jt = ft.joint;
   if (!jt.d || xyzz_out || n == 0 || n > jt.n_t) return false;
@@ -601,24 +683,27 @@ static int joint_msm_impl(Ctx* ctx, FixedTable& ft, const uint32_t* d_scalars, s
   {
     ProfScope p(ctx, st, "msm_accum");
     const size_t bstride = ((size_t)1 << (jt.g - 1)) * packed_words<C>();
+    // the residency reserve's unused dynamic LDS (0 without one: the plain launch)
+    const uint32_t lds = jt.reserve_lds[(glv ? 2 : 0) + (jt.n_inf ? 1 : 0)];
     if (glv && jt.n_inf)
-      hipLaunchKernelGGL((k_joint_accum<C, true, true>), dim3(4 * R, (unsigned)batch), dim3(64), 0, st, ws.jidx, nb,
+      hipLaunchKernelGGL((k_joint_accum<C, true, true>), dim3(4 * R, (unsigned)batch), dim3(64), lds, st, ws.jidx, nb,
                          per, jt.d, bstride, R, ws.fpart);
     else if (glv)
-      hipLaunchKernelGGL((k_joint_accum<C, false, true>), dim3(4 * R, (unsigned)batch), dim3(64), 0, st, ws.jidx, nb,
-                         per, jt.d, bstride, R, ws.fpart);
+      hipLaunchKernelGGL((k_joint_accum<C, false, true>), dim3(4 * R, (unsigned)batch), dim3(64), lds, st, ws.jidx,
+                         nb, per, jt.d, bstride, R, ws.fpart);
     else if (jt.n_inf)
-      hipLaunchKernelGGL((k_joint_accum<C, true>), dim3(4 * R, (unsigned)batch), dim3(64), 0, st, ws.jidx, nb, per,
+      hipLaunchKernelGGL((k_joint_accum<C, true>), dim3(4 * R, (unsigned)batch), dim3(64), lds, st, ws.jidx, nb, per,
                          jt.d, bstride, R, ws.fpart);
     else
-      hipLaunchKernelGGL((k_joint_accum<C, false>), dim3(4 * R, (unsigned)batch), dim3(64), 0, st, ws.jidx, nb, per,
+      hipLaunchKernelGGL((k_joint_accum<C, false>), dim3(4 * R, (unsigned)batch), dim3(64), lds, st, ws.jidx, nb, per,
                          jt.d, bstride, R, ws.fpart);
   }
   {
     ProfScope p(ctx, st, "msm_reduce");
     uint32_t* sums = ws.fsum + batch * (size_t)R * JOINT_NSEG * xyzz_words<C>();
     if (glv) {
-      KZGX_TRY(joint_horner_glv_launch<C>(ws.fpart, (uint32_t)batch, R, ws.fsum, sums, d_out, d_out_inf, st));
+      const bool narrow = jt.reserve_lds[2 + (jt.n_inf ? 1 : 0)] != 0;
+      KZGX_TRY(joint_horner_glv_launch<C>(ws.fpart, (uint32_t)batch, R, ws.fsum, sums, d_out, d_out_inf, narrow, st));
     } else {
       KZGX_TRY(joint_horner_launch<C>(ws.fpart, (uint32_t)batch, R, ws.fsum, sums, st));
       fixed_finish_launch<C>(sums, (uint32_t)batch, d_out, d_out_inf, nullptr, st);

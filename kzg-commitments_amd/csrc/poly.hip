@@ -129,6 +129,7 @@ __global__ __launch_bounds__(256) void k_quotient_single(const uint32_t* __restr
                                                          uint32_t batch, uint32_t* __restrict__ q, size_t qstride,
                                                          uint32_t* __restrict__ ys) {
   constexpr int N = FR::N;
+  __builtin_amdgcn_s_setprio(3);  // a tail pass: issue ahead of a co-resident accumulation (msm_joint.hip "Tail priority")
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t j = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= batch) return;  // whole wavefront
@@ -142,7 +143,10 @@ __global__ __launch_bounds__(256) void k_quotient_single(const uint32_t* __restr
   // phase 2: c_g = sum_{u >= g} local_u z^(L (u - g))
   Fe<FR> c = h;
   Fe<FR> zp = fe_pow_u32<FR>(zm, L);
-#pragma unroll
+  // rolled: unrolled, the six steps' products interleave and the kernel takes
+  // 94 / 96 VGPRs; as a loop 68 / 70, so that its wavefronts fit beside three
+  // of the block table accumulation's per SIMD (msm_joint.hip "Residency reserve")
+#pragma unroll 1
   for (int s = 0; s < 6; s++) {
     Fe<FR> o = fe_shfl_down<FR>(c, 1 << s);
     if (lane + (1u << s) < 64) c = fe_add<FR>(c, fe_mul<FR>(o, zp));  // canonical * Montgomery = canonical

@@ -83,6 +83,45 @@ def kernel_symbols(elf: bytes):
     return out
 
 
+def kernel_descriptors(elf: bytes):
+    """{kernel name: resources} from the 64-byte kernel descriptors (symbols
+    <name>.kd) of a gfx90a-family amdgcn ELF: what a dispatch allocates.
+    vgpr_alloc: VGPRs + AGPRs per lane, (granulated count + 1) x 8; lds: static
+    LDS bytes per workgroup; scratch: private segment bytes per lane (with the
+    frames of the kernel's calls)."""
+    secs = _sections(elf)
+    symoff, symsize, _, _, link, entsize = secs[".symtab"]
+    names = list(secs.keys())
+    strtab_off = secs[names[link]][0]
+    out = {}
+    for k in range(symsize // entsize):
+        st_name, st_info, st_other, st_shndx, st_value, st_size = struct.unpack_from(
+            "<IBBHQQ", elf, symoff + k * entsize)
+        if st_size != 64 or st_shndx == 0 or st_shndx >= len(names):
+            continue
+        end = elf.index(b"\0", strtab_off + st_name)
+        name = elf[strtab_off + st_name:end].decode()
+        if not name.endswith(".kd"):
+            continue
+        sec_off, _, sec_addr = secs[names[st_shndx]][:3]
+        kd = elf[sec_off + (st_value - sec_addr):sec_off + (st_value - sec_addr) + 64]
+        lds, scratch = struct.unpack_from("<II", kd, 0)
+        rsrc1, = struct.unpack_from("<I", kd, 48)
+        out[name[:-3]] = {"vgpr_alloc": ((rsrc1 & 0x3F) + 1) * 8, "lds": lds, "scratch": scratch}
+    return out
+
+
+def kernel_resources(so_path: str, *name_parts: str, target: str = "gfx950") -> dict:
+    """{mangled name: kernel_descriptors entry} of every kernel of the shared
+    object whose mangled name contains all of name_parts"""
+    found = {}
+    for img in device_images(so_path, target):
+        for name, res in kernel_descriptors(img).items():
+            if all(s in name for s in name_parts):
+                found[name] = res
+    return found
+
+
 def mask_pc_relative(code: bytes) -> bytes:
     """the code with the PC-relative offsets of its calls and constant
     addresses zeroed: `s_getpc_b64 s[n:n+1]` (SOP1, op 0x1c) followed by

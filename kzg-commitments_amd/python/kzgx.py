@@ -25,6 +25,7 @@ EXPORTS = [
     "kzgx_set_fixed_base", "kzgx_fixed_base_info", "kzgx_fixed_base_bytes", "kzgx_set_fixed_base_budget",
     "kzgx_set_fixed_base_layout", "kzgx_fixed_base_layout", "kzgx_set_default_table", "kzgx_default_table_info",
     "kzgx_set_fixed_joint", "kzgx_fixed_joint_info", "kzgx_fixed_window_info", "kzgx_set_fixed_joint_ranges",
+    "kzgx_set_fixed_accum_reserve", "kzgx_fixed_accum_reserve_info",
     "kzgx_microbench_mad_u64", "kzgx_microbench_mad_u64_clock", "kzgx_clock_probe", "kzgx_set_fixed_points_per_thread", "kzgx_set_small_batch", "kzgx_microbench_mixed_add", "kzgx_load_srs_g1", "kzgx_gen_srs_g1", "kzgx_get_srs_g1", "kzgx_msm_g1",
     "kzgx_msm_g1_batch", "kzgx_msm_g1_batch_device", "kzgx_quotient_single_batch_device",
     "kzgx_prove_single_batch", "kzgx_prove_single_batch_device", "kzgx_prove_range", "kzgx_poly_eval",
@@ -162,6 +163,8 @@ def lib():
             "kzgx_fixed_joint_info": (ctypes.c_int, [vp, intp, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
             "kzgx_fixed_window_info": (ctypes.c_int, [vp, intp, ctypes.POINTER(sz)]),
             "kzgx_set_fixed_joint_ranges": (ctypes.c_int, [vp, ctypes.c_uint]),
+            "kzgx_set_fixed_accum_reserve": (ctypes.c_int, [vp, ctypes.c_int]),
+            "kzgx_fixed_accum_reserve_info": (ctypes.c_int, [vp, intp, intp, ctypes.POINTER(sz), intp]),
             "kzgx_set_default_table": (ctypes.c_int, [vp, ctypes.c_int, sz]),
             "kzgx_default_table_info": (ctypes.c_int, [vp, intp, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
             "kzgx_fixed_base_layout": (ctypes.c_int, [vp, intp]),
@@ -596,6 +599,28 @@ class Context:
     def set_fixed_joint_ranges(self, ranges: int):
         """block ranges per MSM of the block table's accumulation (0 = automatic)"""
         _chk(lib().kzgx_set_fixed_joint_ranges(self.h, ranges), "kzgx_set_fixed_joint_ranges")
+
+    def set_fixed_accum_reserve(self, r: int):
+        """wave slots per CU that the block table's accumulation leaves free for the other
+        stream's tail passes (-1 = the curve's default, 0 = none; clamped to what the device allows)"""
+        _chk(lib().kzgx_set_fixed_accum_reserve(self.h, r), "kzgx_set_fixed_accum_reserve")
+
+    def fixed_accum_reserve_info(self):
+        """(request, reserve in effect, dynamic LDS bytes per accumulation workgroup that hold it)"""
+        req = ctypes.c_int(0)
+        r = ctypes.c_int(0)
+        b = sz(0)
+        _chk(lib().kzgx_fixed_accum_reserve_info(self.h, ctypes.byref(req), ctypes.byref(r), ctypes.byref(b), None),
+             "kzgx_fixed_accum_reserve_info")
+        return req.value, r.value, b.value
+
+    def fixed_accum_variant(self):
+        """the accumulation kernel the next block-table call launches: bit 0 = tests for entries at
+        infinity, bit 1 = the endomorphism split's"""
+        v = ctypes.c_int(0)
+        _chk(lib().kzgx_fixed_accum_reserve_info(self.h, None, None, None, ctypes.byref(v)),
+             "kzgx_fixed_accum_reserve_info")
+        return v.value
 
     def fixed_joint_info(self):
         """(block size g, blocks, device bytes) of the built block table, g = 0: none"""
